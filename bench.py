@@ -9,7 +9,16 @@ buffered tile buffers); the timed region ends when every frame is assembled.  Th
 before timing (synthetic, seeded) and replicated per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1024x8]
+  python bench.py ... --full                # + roofline, PMC traffic, parity, CPU baseline
+  python bench.py ... --dump-outputs DIR    # the last timed frame as DIR/*.npy
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it generates the volume,
+warms up, times the K steps and prints the line (metric, value, unit,
+ms_per_step, ...; the fields of the untimed extras are null).  --full adds the
+untimed extras, each a run of its own: the footprint count and read ceiling of
+the roofline, the committed PMC traffic, the one-tile latency probe, the
+whole-frame re-render and its parity against the CPU oracle, the CPU baseline.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts
 its own N ranks: a child `python -m torch.distributed.run --nproc-per-node N
@@ -135,9 +144,16 @@ def parse():
     ap.add_argument("--baked", action="store_true",
                     help="basicDataProcessing first: frames filter the baked statistics "
                          "planes (vr_stats.hip) instead of decoding records per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed extras: roofline (footprint count, read "
+                         "ceiling, PMC traffic, latency probe), parity re-render, CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the frame of the last timed step to DIR as float32 "
+                         ".npy (frame_rgba8.npy: H x W x 4 channel values 0..255)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline (and its oracle parity)")
     ap.add_argument("--no-issue-bounds", action="store_true",
-                    help="skip the untimed one-tile latency probe (roofline.compute): "
+                    help="--full without the untimed one-tile latency probe (roofline.compute): "
                          "profiling runs use it so a kernel's rocprofv3 average holds only "
                          "whole-frame launches")
     ap.add_argument("--render-streams", type=int, default=0, choices=[0, 1, 2],
@@ -171,7 +187,30 @@ def parse():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-measured HBM bytes per launch (tools/pmc_traffic.py) for "
                          "roofline.traffic; used only when the kernel matches")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_issue_bounds = True
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE_PIXELS = 1 << 20  # pixels kept of a frame larger than that
+
+
+def dump_outputs(directory, frame8):
+    """--dump-outputs: what a caller of the timed path receives, the packed RGBA8
+    frame of the last timed step (H x W uint32, d_output of vr.h), as float32
+    channel values 0..255 (exact) in DIR/frame_rgba8.npy, H x W x 4.  A frame over
+    64 MB that way (3840x2160) is written as a fixed seeded sample of its pixels:
+    frame_rgba8.npy n x 4, their flat pixel indices in sample_pixels.npy (f64)."""
+    os.makedirs(directory, exist_ok=True)
+    h, w = frame8.shape
+    rgba = np.ascontiguousarray(frame8).view(np.uint8).reshape(h, w, 4).astype(np.float32)
+    if rgba.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(SEED).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+        rgba = rgba.reshape(h * w, 4)[idx]
+        np.save(os.path.join(directory, "sample_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "frame_rgba8.npy"), rgba)
 
 
 def camera_matrix(pkg, cam):
@@ -600,6 +639,8 @@ def gmm_slab_rehearsal(args, pkg, torch, dev, stream, m, n, K, W, H, rec_bytes):
         r["bytes_out"] = r["rays_out"] * pkg.slabs.RAY_WORDS * 4
     period = serial
     kernel = pkg.last_kernel()
+    if args.dump_outputs:  # the frame the last chain's slabs wrote
+        dump_outputs(args.dump_outputs, frame.cpu().numpy().view(np.uint32).reshape(H, W))
     worst = max(rows_bal, key=lambda r: r["ms"])
     cpu = None if args.no_cpu_baseline else gmm_cpu_baseline(m, args.method, W, H, K)
     out = {
@@ -814,9 +855,15 @@ def gmm_two_segment_run(args, pkg, torch, dist, dev, stream, m, n, K, W, H, rank
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
-    if args.dump_frame and rank == 0:
-        last = frames[(F - 1) % RING]
-        np.save(args.dump_frame, last.cpu().numpy().view(np.uint32).reshape(H, W))
+    if (args.dump_frame or args.dump_outputs) and rank == 0:
+        last = frames[(F - 1) % RING].cpu().numpy().view(np.uint32).reshape(H, W)
+        if args.dump_frame:
+            np.save(args.dump_frame, last)
+        if args.dump_outputs:
+            # the frame the last timed tick completed (the ring is longer than the
+            # 2R frames drained after it, so its buffer still holds it)
+            timed = frames[(args.warmup + args.steps - 1) % RING]
+            dump_outputs(args.dump_outputs, timed.cpu().numpy().view(np.uint32).reshape(H, W))
     out = None
     if rank == 0:
         phys = min(world, max(ndev, 1))
@@ -1018,7 +1065,8 @@ def main_gmm(args):
             z_lo, z_hi = regenerate(bounds)
         balanced = True
     # U before the warm-up (as in main(): the counting pass warms clocks and translation)
-    u = pkg.gmm_count_footprint(desc) if world == 1 else None
+    # (--full: the count is a march of its own)
+    u = pkg.gmm_count_footprint(desc) if world == 1 and args.full else None
     for _ in range(args.warmup):
         step(False)
     drain()
@@ -1039,11 +1087,14 @@ def main_gmm(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    if args.dump_frame and rank == 0:
-        last = frames[(nframe[0] - 1) % R]
-        np.save(args.dump_frame, last.cpu().numpy().view(np.uint32).reshape(H, W))
+    if (args.dump_frame or args.dump_outputs) and rank == 0:
+        last = frames[(nframe[0] - 1) % R].cpu().numpy().view(np.uint32).reshape(H, W)
+        if args.dump_frame:
+            np.save(args.dump_frame, last)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
     kernel = pkg.last_kernel()
-    pmc, traffic_src = traffic_entry(args, kernel, world)
+    pmc, traffic_src = traffic_entry(args, kernel, world) if args.full else (None, None)
     traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
     alg_bytes = u * rec_bytes + W * H * 4 if u is not None else None
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if alg_bytes else None
@@ -1201,12 +1252,14 @@ def main():
     # Counted before the warm-up: the counting pass marches the same footprints once,
     # so the frames that follow start with the clocks and the address translation
     # of a running frame loop (profiles/r02/loop_timing.log)
+    # (--full: the count is a march of its own)
     pixels = W * H if world == 1 else int(np.sum(lists[rank] != pkg.tiles.PAD)) * 256
-    u = pkg.count_footprint(desc) if args.method in (1, 2, 3) else None
+    u = pkg.count_footprint(desc) if args.full and args.method in (1, 2, 3) else None
     # baked frames read one f32 statistic per footprint voxel instead of the record
     rec_bytes = 4 if args.baked else nb * 4
     vol_bytes = (u * rec_bytes if u is not None
-                 else pkg.footprint_bytes(desc) if args.method in (4, 5, 6) and not args.baked
+                 else pkg.footprint_bytes(desc)
+                 if args.full and args.method in (4, 5, 6) and not args.baked
                  else None)
     alg_bytes = (vol_bytes + pixels * 4) if vol_bytes is not None else None
     torch.cuda.synchronize()
@@ -1217,14 +1270,18 @@ def main():
     # clocks of a loaded GPU (the frame time settles over the first ~50 ms of work,
     # DESIGN.md section 6)
     # (a codec volume, methods 4/5/6, has no record volume to stream: none)
+    # A plain run makes the same passes, as part of its warm-up: they are what puts
+    # the timed frames on a loaded GPU's clocks whatever --warmup is; only --full
+    # reports them as the ceiling.
     ceiling = None
     if world == 1 and args.method not in (4, 5, 6):
         rb, rms, rmean = pkg.stream_read(8)
-        ceiling = {"kernel": "k_stream_read", "bytes": rb, "ms": round(rms, 4),
-                   "mean_ms": round(rmean, 4), "GBps": round(rb / (rms * 1e-3) / 1e9, 1),
-                   "frac_of_peak": round(rb / (rms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                   "what": "the resident record volume (pitches included) read once per "
-                           "pass, 16 B per lane, fastest of 8 timed passes"}
+        if args.full:
+            ceiling = {"kernel": "k_stream_read", "bytes": rb, "ms": round(rms, 4),
+                       "mean_ms": round(rmean, 4), "GBps": round(rb / (rms * 1e-3) / 1e9, 1),
+                       "frac_of_peak": round(rb / (rms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                       "what": "the resident record volume (pitches included) read once per "
+                               "pass, 16 B per lane, fastest of 8 timed passes"}
     torch.cuda.synchronize()
 
     ev = []
@@ -1301,7 +1358,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     pkg.set_stream(stream)  # (N > 1: the loop left the library on the last frame's stream)
-    if world > 1:
+    if args.dump_outputs and rank == 0:  # the frame of the last timed step, before any extra
+        dump_outputs(args.dump_outputs, frame.cpu().numpy().view(np.uint32).reshape(H, W))
+    if world > 1 and args.full:
         # this rank's render alone (untimed, after the loop): HIP events around 5
         # renders of its list; the line reports the max over ranks
         torch.cuda.synchronize()
@@ -1313,9 +1372,9 @@ def main():
                 e1.record(stream)
                 ev.append((e0, e1))
         torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else None
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank's (alg bytes, U, render ms, pixels), summed into a world x 4
         # table: the whole-node roofline (aggregate_roofline)
         per_rank = torch.zeros((world, 4), dtype=torch.float64,
@@ -1333,8 +1392,9 @@ def main():
     # HBM bytes per launch from the committed PMC passes of this same workload
     # (tools/pmc_traffic.py; FETCH_SIZE x 2 + WRITE_SIZE), only if they were
     # measured on this very libvr.so build (sha256 of the file) and kernel
-    pmc, traffic_src = traffic_entry(args, kernel, world,
-                                     lists_sha16(lists) if world > 1 else None, rank)
+    pmc, traffic_src = (traffic_entry(args, kernel, world,
+                                      lists_sha16(lists) if world > 1 else None, rank)
+                        if args.full else (None, None))
     rank_traffic = pmc.get("per_rank_hbm_bytes") if pmc and world > 1 else None
     traffic = (rank_traffic[rank] if rank_traffic else None) if world > 1 else (
         pmc.get("hbm_bytes_per_launch") if pmc else None)
@@ -1346,7 +1406,7 @@ def main():
     # against the oracle frame of the CPU baseline below, N > 1 assembled frames
     # against rank 0's own whole-frame render)
     check = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.cuda.stream(stream):
             g8 = torch.zeros(W * H, dtype=torch.int32, device=dev)
             gf = torch.zeros(W * H * 4, dtype=torch.float32, device=dev)
@@ -1380,7 +1440,7 @@ def main():
             if world > 1:
                 parity = assembled_parity(frame.cpu().numpy().view(np.uint32).reshape(H, W),
                                           ref, stride, world, parity)
-        elif world > 1:
+        elif world > 1 and args.full:
             got = frame.cpu().numpy().view(np.uint32).reshape(H, W)
             parity = {"against": "rank 0's whole-frame render of the same view (no oracle: "
                                  "--no-cpu-baseline)",
@@ -1429,7 +1489,7 @@ def main():
                 "traffic": traffic,
                 "traffic_source": traffic_src,
                 "kernel": kernel,
-                "kernel_ms": round(kern_ms, 4),
+                "kernel_ms": round(kern_ms, 4) if kern_ms is not None else None,
                 "alg_bytes_per_launch": int(alg_bytes) if alg_bytes else None,
                 "U_records": int(u) if u is not None else None,
                 "compute": bounds,

@@ -142,6 +142,40 @@ def test_assembled_parity_counts_every_pixel_of_the_oracle_rows():
     assert p["row_stride"] == 2 and "4 ranks" in p["frame"]
 
 
+def test_dump_outputs_writes_float32_channels_and_samples_large_frames(tmp_path, monkeypatch):
+    """--dump-outputs: the packed RGBA8 frame as exact float32 channel values; a
+    frame over the byte limit as the same seeded sample of pixels every time"""
+    import numpy as np
+    b = _bench()
+    frame = (np.arange(6 * 5, dtype=np.uint32) * 0x01020381).reshape(6, 5)
+    b.dump_outputs(str(tmp_path / "a"), frame)
+    assert os.listdir(tmp_path / "a") == ["frame_rgba8.npy"]
+    rgba = np.load(tmp_path / "a" / "frame_rgba8.npy")
+    assert rgba.dtype == np.float32 and rgba.shape == (6, 5, 4)
+    assert np.array_equal(rgba.astype(np.uint8).reshape(6, 20).view(np.uint32), frame)
+    assert rgba[1, 1].tolist() == [float(v) for v in np.uint32(6 * 0x01020381).tobytes()]
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 6 * 5 * 16 - 1)
+    monkeypatch.setattr(b, "DUMP_SAMPLE_PIXELS", 7)
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), frame)
+    idx = np.load(tmp_path / "b" / "sample_pixels.npy")
+    assert idx.dtype == np.float64 and len(set(idx.tolist())) == 7 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "sample_pixels.npy"))
+    sample = np.load(tmp_path / "b" / "frame_rgba8.npy")
+    assert sample.dtype == np.float32
+    assert np.array_equal(sample, rgba.reshape(30, 4)[idx.astype(np.int64)])
+
+
+def test_plain_run_switches_the_untimed_extras_off(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert not a.full and a.no_cpu_baseline and a.no_issue_bounds and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = b.parse()
+    assert a.full and not a.no_cpu_baseline and not a.no_issue_bounds and not a.dump_outputs
+
+
 def test_lists_sha_identifies_a_deal():
     import numpy as np
     b = _bench()

@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--config", "256x4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+ARGS = ["--config", "256x4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
 
 
 def _run(cmd, tmp_path):
@@ -83,10 +83,34 @@ def test_bench_single_and_two_rank_frames_agree(gpu, tmp_path):
     assert np.array_equal(a, b), f"{int(np.sum(a != b))} pixels differ between N=1 and N=2"
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_frame(gpu, tmp_path):
+    """without --full: the timed steps only (the extras' fields null), and
+    --dump-outputs writes the last timed frame as float32 channel values"""
+    f1, d = str(tmp_path / "f.npy"), tmp_path / "dump"
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--config", "256x4", "--steps", "3",
+                "--warmup", "1", "--dump-frame", f1, "--dump-outputs", str(d)], tmp_path)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["value"] > 0 and out["unit"] == "Mrays/s" and out["higher_is_better"] is True
+    assert out["dtype"] and "256^3 x 4-bin" in out["metric"]
+    # value = W*H / t_frame (Mrays/s), t_frame = ms_per_step (both rounded in the line)
+    assert out["value"] == pytest.approx(512 * 512 / out["ms_per_step"] / 1e3, rel=1e-2)
+    assert out["cpu_baseline"] is None and out["parity"] is None
+    rf = out["roofline"]
+    assert rf["kernel"].startswith("k_march") and rf["kernel_ms"] > 0
+    for k in ("achieved", "frac", "traffic", "U_records", "compute", "read_ceiling",
+              "gather_bytes_per_launch"):
+        assert rf[k] is None, k
+    assert sorted(p.name for p in d.iterdir()) == ["frame_rgba8.npy"]
+    rgba, packed = np.load(d / "frame_rgba8.npy"), np.load(f1)
+    assert rgba.dtype == np.float32 and rgba.shape == (512, 512, 4)
+    assert np.count_nonzero(packed) > 0
+    assert np.array_equal(rgba.astype(np.uint8).reshape(512, 512 * 4).view(np.uint32), packed)
+
+
 def test_bench_gmm_single_and_two_slab_frames_agree(gpu, tmp_path):
     """GMM mode: the whole-volume frame (N = 1) equals the 2-rank z-slab chain's
     (alive rays handed rank to rank, frames summed on rank 0; gloo staging)"""
-    args = ["--config", "gmm96", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    args = ["--config", "gmm96", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     f1 = str(tmp_path / "g1.npy")
     out1 = _run([sys.executable, "bench.py", *args, "--dump-frame", f1], tmp_path)
     assert out1["n_gpus"] == 1 and out1["value"] > 0
@@ -118,7 +142,7 @@ def test_bench_gmm_slab_rehearsal(gpu, tmp_path):
     for seg in ("1", "2"):
         out = _run([sys.executable, "bench.py", "--config", "gmm96", "--slab-rehearsal",
                     "--rehearsal-ranks", "3", "--segments", seg, "--steps", "2", "--warmup", "1",
-                    "--no-cpu-baseline"], tmp_path)
+                    "--full", "--no-cpu-baseline"], tmp_path)
         cfg = out["config"]
         assert out["n_gpus"] == 1 and out["scaling"] is None and out["rehearsal_shared_gpus"]
         assert len(cfg["slabs_balanced"]) == 3 * int(seg)

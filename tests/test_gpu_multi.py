@@ -26,7 +26,7 @@ def test_rccl_ranks_assemble_the_single_gpu_frame(gpu, tmp_path, args, shape):
         pytest.skip("needs >= 2 GPUs (RCCL ranks on distinct devices)")
     import sys
     import numpy as np
-    common = args + ["--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    common = args + ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     f1 = str(tmp_path / "n1.npy")
     out1 = _run([sys.executable, "bench.py", *common, "--dump-frame", f1], tmp_path)
     f2 = str(tmp_path / "n2.npy")

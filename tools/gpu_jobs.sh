@@ -58,13 +58,13 @@ pmcb)
     i=$((i+1))
     for W in "C0 --baked" "C1 --baked" "C0"; do
       N=$(echo $W | tr -d ' -')
-      timeout -s KILL 120 rocprofv3 --pmc $CTRS --output-format csv -d $O/$N/p$i -o p$i -- python bench.py --camera $W --no-cpu-baseline --no-issue-bounds --steps 3 --warmup 1 > $O/${N}_p$i.log 2>&1; guard $? pmc-$N-$i $O/${N}_p$i.log
+      timeout -s KILL 120 rocprofv3 --pmc $CTRS --output-format csv -d $O/$N/p$i -o p$i -- python bench.py --camera $W --full --no-cpu-baseline --no-issue-bounds --steps 3 --warmup 1 > $O/${N}_p$i.log 2>&1; guard $? pmc-$N-$i $O/${N}_p$i.log
     done
   done < tools/pmc_sets.txt ;;
 wide)
   for W in "1024x32 C0 1" "1024x32 C1 1" "1024x32 C0 3" "1024x16 C0 1" "1024x16 C1 1" "512x32 C0 1" "512x32 C1 1"; do
     read CFG CAM M <<< "$W"
-    timeout -k 10 300 python -u bench.py --config $CFG --camera $CAM --method $M --no-cpu-baseline > $O/bench_${CFG}_${CAM}_m$M.log 2>&1; guard $? wide-$CFG $O/bench_${CFG}_${CAM}_m$M.log
+    timeout -k 10 300 python -u bench.py --config $CFG --camera $CAM --method $M --full --no-cpu-baseline > $O/bench_${CFG}_${CAM}_m$M.log 2>&1; guard $? wide-$CFG $O/bench_${CFG}_${CAM}_m$M.log
   done ;;
 *) echo "unknown job $J"; exit 2 ;;
 esac
