@@ -167,6 +167,40 @@ int vr_init_distribution(const float *bins, vr_extent dims, int nbins, int where
  * directly in HBM (library-owned). */
 int vr_synthesize(vr_extent dims, int nbins, uint64_t seed);
 
+/* f16 record volumes: the bins stored as IEEE binary16,
+ * half the HBM bytes per voxel.  f16 -> f32 widening is exact, so an f16 volume
+ * renders bit-identically to the fp32 volume of the same records widened.
+ *
+ * vr_init_distribution_f16: as vr_init_distribution (same AoS layout, `where`
+ * values and pitches) with 2-byte elements.  nbins must be one of 1, 2, 4, 8,
+ * 16, 32 (VR_ERR_UNSUPPORTED otherwise); an adopted pointer (where == 2) must
+ * be aligned to min(16, 2 * nbins) bytes (VR_ERR_ARG otherwise).
+ *
+ * vr_convert_f16: narrows the resident fp32 record volume to f16 on the device
+ * (round to nearest even, subnormals kept) into a new library-owned buffer
+ * with the same record pitches, then releases the fp32 one (freed if the
+ * library owned it, forgotten if it was adopted); peak memory 1.5x the fp32
+ * volume.  Baked planes and layout copies are dropped, as by a re-upload.
+ * VR_ERR_STATE if no volume is resident or it is f16 already,
+ * VR_ERR_UNSUPPORTED for other bin counts than the six above.
+ *
+ * vr_volume_dtype: VR_DTYPE_F32 / VR_DTYPE_F16 of the resident record volume,
+ * VR_ERR_STATE without one.
+ *
+ * What an f16 volume serves: methods 1/2/3 per step through one kernel family
+ * (k_march_pipe_h, every view on the x rows; no micro-brick or axis-rows copy
+ * is made, VR_PATH / VR_SEG / VR_WIDE do not apply, VR_WG_PER_CU does);
+ * vr_bake_stats and with it baked methods 1/2/3/7; tile lists, d_output_f,
+ * d_steps, clipped renders; vr_count_footprint, vr_footprint_bytes (U * nbins
+ * * 2), vr_stream_read (the real byte size).  Method 7 on an unbaked f16 volume
+ * is VR_ERR_UNSUPPORTED (bake first).  Codec, flexible-block and GMM volumes
+ * are separate state and always fp32. */
+#define VR_DTYPE_F32 0
+#define VR_DTYPE_F16 1
+int vr_init_distribution_f16(const void *bins, vr_extent dims, int nbins, int where);
+int vr_convert_f16(void);
+int vr_volume_dtype(void);
+
 /* Fractal/template codec volume for methods 4/5/6 (the initCuda arrays of
  * K:1893-1900, as the reference's loaders fill them, C:558-675):
  *   codebook  dims.width*height*depth x (template id, shift, flip, NE), voxel
@@ -233,7 +267,8 @@ int vr_flex_process(int block);
  * entropy, 0), block (x, y, z) at x + n*(y + n*z)) of the resident statistics */
 int vr_flex_info(int *nblk, int *nbins, const float **d_blocks);
 
-/* dims, bin count and device pointer of the resident volume */
+/* dims, bin count and device pointer of the resident volume (for an f16 volume,
+ * vr_volume_dtype, *d_bins addresses 2-byte halves despite its type) */
 int vr_volume_info(vr_extent *dims, int *nbins, const float **d_bins);
 
 /* Record pitch of a voxel row and of a slice of the resident volume in HBM
@@ -291,7 +326,7 @@ int vr_render(const vr_render_desc *desc);
 int64_t vr_count_footprint(const vr_render_desc *desc);
 
 /* Algorithmic bytes of one launch's volume reads: methods
- * 1/2/3: U * nbins * 4; methods 4/5/6: 16 bytes of codebook and 8 bytes per
+ * 1/2/3: U * nbins * 4 (f16 volume: * 2); methods 4/5/6: 16 bytes of codebook and 8 bytes per
  * used error pair for every distinct voxel the footprints touch, plus the
  * template table once.  Synchronous.  Returns bytes or a negative status. */
 int64_t vr_footprint_bytes(const vr_render_desc *desc);

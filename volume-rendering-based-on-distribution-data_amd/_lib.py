@@ -18,6 +18,8 @@ VR_ERR_ARG = -1
 VR_ERR_STATE = -2
 VR_ERR_HIP = -3
 VR_ERR_UNSUPPORTED = -4
+VR_DTYPE_F32 = 0
+VR_DTYPE_F16 = 1
 
 
 class VRError(RuntimeError):
@@ -99,7 +101,7 @@ EXPORTS = [
     "vr_init_gmm", "vr_synthesize_gmm", "vr_gmm_info", "vr_free_gmm", "vr_gmm_select", "vr_render_gmm",
     "vr_gmm_count_footprint", "vr_gmm_count_footprint_slab", "vr_bake_stats", "vr_release_stats", "vr_stats_info",
     "vr_set_tuning", "vr_clear_tuning", "vr_stream_read", "vr_set_layout_budget",
-    "vr_layout_info",
+    "vr_layout_info", "vr_init_distribution_f16", "vr_convert_f16", "vr_volume_dtype",
 ]
 
 _lib = None
@@ -138,6 +140,12 @@ def load() -> ctypes.CDLL:
     L.vr_clear_error.restype = None
     L.vr_init_distribution.argtypes = [vp, Extent, i32, i32]
     L.vr_init_distribution.restype = i32
+    L.vr_init_distribution_f16.argtypes = [vp, Extent, i32, i32]
+    L.vr_init_distribution_f16.restype = i32
+    L.vr_convert_f16.argtypes = []
+    L.vr_convert_f16.restype = i32
+    L.vr_volume_dtype.argtypes = []
+    L.vr_volume_dtype.restype = i32
     L.vr_synthesize.argtypes = [Extent, i32, ctypes.c_uint64]
     L.vr_synthesize.restype = i32
     L.vr_volume_info.argtypes = [ctypes.POINTER(Extent), ctypes.POINTER(ctypes.c_int),

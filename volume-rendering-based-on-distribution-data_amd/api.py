@@ -287,7 +287,12 @@ def init_distribution(bins, nbins: Optional[int] = None, dims=None, adopt: bool 
 
     bins: numpy array (nz, ny, nx, B) -> copied from host; or a torch CUDA tensor
     of the same shape -> copied device-to-device (adopt=False) or used in place
-    (adopt=True, the caller keeps it alive)."""
+    (adopt=True, the caller keeps it alive).
+
+    A numpy.float16 array or a torch.float16 CUDA tensor becomes resident as an
+    f16 volume (half the bytes per voxel, B in 1, 2, 4, 8, 16, 32; volume_dtype()
+    == "f16"); it renders bit-identically to the same records widened to
+    float32.  Every other input is taken as float32, as before."""
     L = _lib.load()
     if hasattr(bins, "data_ptr") and getattr(bins, "is_cuda", False):
         shp = tuple(bins.shape)
@@ -295,14 +300,30 @@ def init_distribution(bins, nbins: Optional[int] = None, dims=None, adopt: bool 
             nz, ny, nx, nb = shp
             dims = (nx, ny, nz)
         nb = nbins if nbins is not None else shp[-1]
-        check(L.vr_init_distribution(_ptr(bins), _extent(dims), int(nb), 2 if adopt else 1))
+        init = (L.vr_init_distribution_f16 if str(bins.dtype) == "torch.float16"
+                else L.vr_init_distribution)
+        check(init(_ptr(bins), _extent(dims), int(nb), 2 if adopt else 1))
         return
-    a = np.ascontiguousarray(np.asarray(bins, dtype=np.float32))
+    half = isinstance(bins, np.ndarray) and bins.dtype == np.float16
+    a = np.ascontiguousarray(np.asarray(bins, dtype=np.float16 if half else np.float32))
     if dims is None:
         nz, ny, nx, nb = a.shape
         dims = (nx, ny, nz)
     nb = nbins if nbins is not None else a.shape[-1]
-    check(L.vr_init_distribution(a.ctypes.data, _extent(dims), int(nb), 0))
+    init = L.vr_init_distribution_f16 if half else L.vr_init_distribution
+    check(init(a.ctypes.data, _extent(dims), int(nb), 0))
+
+
+def convert_f16() -> None:
+    """Narrow the resident float32 record volume to f16 on the device (round to
+    nearest even, subnormals kept); baked planes and layout copies are dropped.
+    synthesize() then convert_f16() makes a large synthetic f16 volume."""
+    check(_lib.load().vr_convert_f16())
+
+
+def volume_dtype() -> str:
+    """"f32" or "f16": the element type of the resident record volume."""
+    return "f16" if check(_lib.load().vr_volume_dtype()) == _lib.VR_DTYPE_F16 else "f32"
 
 
 def synthesize_codec(dims, nbins: int, ntemplates: int = 64, slots: int = 4,
@@ -542,6 +563,6 @@ __all__ = [
     "set_stream", "set_tuning", "clear_tuning", "make_desc", "render", "count_footprint", "footprint_bytes", "unscatter_tiles", "last_kernel", "debug_wave_clock", "stream_read", "version",
     "init_gmm", "synthesize_gmm", "gmm_info", "free_gmm", "gmm_select", "gmm_slab", "render_gmm",
     "gmm_count_footprint", "bake_stats", "release_stats", "stats_info", "set_layout_budget",
-    "layout_info",
+    "layout_info", "convert_f16", "volume_dtype",
     "VRError", "PAD",
 ]

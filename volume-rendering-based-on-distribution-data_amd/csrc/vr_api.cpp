@@ -21,6 +21,7 @@ namespace {
 
 struct State {
     float *vol = nullptr;
+    int dtype = VR_DTYPE_F32;       // element type of vol's bins (F16: vol addresses halves)
     bool owned = false;
     int nx = 0, ny = 0, nz = 0, nb = 0;
     uint64_t sy = 0, sz = 0;        // record pitch of a voxel row / slice in HBM
@@ -197,9 +198,13 @@ uint64_t layout_resident() {
 // of view needs, not every copy at once (a third record copy replaces one).
 // Plus 64 MiB: a volume a few cells wide pads its 2 x 2 micro-bricks by up to
 // 4x, far beyond 1/8, and copies that small cost nothing worth refusing.
+// bytes of one bin of the resident record volume
+uint64_t elem_bytes() { return g.dtype == VR_DTYPE_F16 ? 2 : sizeof(float); }
+bool is_f16() { return g.vol && g.dtype == VR_DTYPE_F16; }
+
 uint64_t layout_budget_bytes() {
     if (g.layout_budget != UINT64_MAX) return g.layout_budget;
-    const uint64_t rec = g.vol ? g.sz * (uint64_t)g.nz * g.nb * sizeof(float) : 0;
+    const uint64_t rec = g.vol ? g.sz * (uint64_t)g.nz * g.nb * elem_bytes() : 0;
     const uint64_t plane = g.stats ? g.stats_plane * sizeof(float) : 0;
     return 2 * (rec + rec / 8) + 3 * (plane + plane / 8) + (64ull << 20);
 }
@@ -223,6 +228,7 @@ void release_volume() {
     g.volume_epoch++;
     if (g.vol && g.owned) (void)hipFree(g.vol);
     g.vol = nullptr;
+    g.dtype = VR_DTYPE_F32;
     g.owned = false;
     g.nx = g.ny = g.nz = g.nb = 0;
     g.sy = g.sz = 0;
@@ -938,7 +944,8 @@ int bake_stats() {
         float *buf = nullptr;
         VR_HIP(hipMalloc(&buf, (4 * plane + 4) * sizeof(float)));
         hipError_t e = hipMemsetAsync(buf, 0, (4 * plane + 4) * sizeof(float), g.stream);
-        if (e == hipSuccess) e = vr::launch_bake_raw(g.vol, P, buf, plane, psy, psz, g.stream);
+        if (e == hipSuccess)
+            e = vr::launch_bake_raw(g.vol, is_f16(), P, buf, plane, psy, psz, g.stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
         if (e != hipSuccess) {
             (void)hipFree(buf);
@@ -1011,7 +1018,7 @@ bool ensure_brick() {
     if (const char *e = vr::tuning("VR_BRICK"))
         if (std::atoi(e) == 0) return false;
     if (g.brick) return true;
-    if (!g.vol || !g.owned || g.nb != 8) return false;
+    if (!g.vol || !g.owned || g.nb != 8 || is_f16()) return false;  // fp32 records only
     const uint64_t nxp = (uint64_t)g.nx + (g.nx & 1), nyp = (uint64_t)g.ny + (g.ny & 1);
     const uint64_t bsy = 2 * nxp, bsz = nxp * nyp;
     const uint64_t bytes = bsz * (uint64_t)g.nz * 8 * sizeof(float);
@@ -1062,6 +1069,7 @@ bool ensure_axis_copy(int axis) {
     const int i = axis - 1, other = 1 - i;
     if (g.acopy[i].buf) return true;
     if (!g.vol || !g.owned || !(g.nb == 1 || g.nb == 2 || g.nb == 4 || g.nb == 8)) return false;
+    if (is_f16()) return false;  // fp32 records only
     uint64_t sx = 0, sy = 0, sz = 0;
     vr::axis_copy_strides(axis, (uint64_t)g.nx, (uint64_t)g.ny, (uint64_t)g.nz, sx, sy, sz);
     const uint64_t bytes = (uint64_t)g.nx * g.ny * (uint64_t)g.nz * (uint64_t)g.nb * sizeof(float);
@@ -1228,7 +1236,7 @@ const char *vr_last_kernel(void) { return vr::last_march_kernel(); }
 int vr_stream_read(int reps, float *ms, uint64_t *bytes) {
     if (!ms || reps < 1) return fail(VR_ERR_ARG, "vr_stream_read: ms null or reps < 1");
     if (!g.vol) return fail(VR_ERR_STATE, "no volume resident");
-    const uint64_t nbytes = (g.sz * (uint64_t)g.nz * (uint64_t)g.nb * 4u) & ~(uint64_t)15;
+    const uint64_t nbytes = (g.sz * (uint64_t)g.nz * (uint64_t)g.nb * elem_bytes()) & ~(uint64_t)15;
     hipDevice_t dev;
     int dev_id = 0, cus = 0;
     VR_HIP(hipGetDevice(&dev_id));
@@ -1475,49 +1483,105 @@ int vr_flex_info(int *nblk, int *nbins, const float **d_blocks) {
     return g.flex.blocks ? VR_OK : fail(VR_ERR_STATE, "no flexible-block statistics resident");
 }
 
-int vr_init_distribution(const float *bins, vr_extent dims, int nbins, int where) {
+// vr_init_distribution / vr_init_distribution_f16: bins of `elem` bytes each
+static int init_records(const void *bins, vr_extent dims, int nbins, int where, int dtype) {
+    const size_t elem = dtype == VR_DTYPE_F16 ? 2 : sizeof(float);
     if (!bins) return fail(VR_ERR_ARG, "null distribution pointer");
     if (nbins < 1) return fail(VR_ERR_ARG, "nbins must be >= 1 (got %d)", nbins);
     if (dims.width == 0 || dims.height == 0 || dims.depth == 0)
         return fail(VR_ERR_ARG, "empty volume");
     if (dims.width > 65536 || dims.height > 65536 || dims.depth > 65536)
         return fail(VR_ERR_ARG, "volume dimension > 65536");
+    if (dtype == VR_DTYPE_F16) {
+        if (nbins != 1 && nbins != 2 && nbins != 4 && nbins != 8 && nbins != 16 && nbins != 32)
+            return fail(VR_ERR_UNSUPPORTED, "f16 volumes with %d bins (compiled: 1,2,4,8,16,32)",
+                        nbins);
+        // a record is read in loads of up to 16 bytes (vr_half.h load_rec_h)
+        const size_t align = std::min<size_t>(16, 2 * (size_t)nbins);
+        if (where == 2 && reinterpret_cast<uintptr_t>(bins) % align != 0)
+            return fail(VR_ERR_ARG, "an adopted f16 volume of %d bins must be aligned to %zu bytes",
+                        nbins, align);
+    }
     release_volume();
     const int nx = (int)dims.width, ny = (int)dims.height, nz = (int)dims.depth;
     uint64_t sy, sz;
     if (where == 2) {  // adopted buffer keeps its dense AoS layout
         sy = (uint64_t)nx;
         sz = sy * (uint64_t)ny;
-        g.vol = const_cast<float *>(bins);
+        g.vol = static_cast<float *>(const_cast<void *>(bins));
         g.owned = false;
     } else {
         choose_pitch(nx, ny, sy, sz);
-        const size_t rec = (size_t)nbins * sizeof(float);
-        float *d = nullptr;
+        const size_t rec = (size_t)nbins * elem;
+        char *d = nullptr;
+        const char *src = static_cast<const char *>(bins);
         VR_HIP(hipMalloc(&d, sz * (size_t)nz * rec));
         const hipMemcpyKind kind = where == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
         hipError_t e = hipSuccess;
         if (sy == (uint64_t)nx && sz == sy * (uint64_t)ny) {
-            e = hipMemcpy(d, bins, sz * (size_t)nz * rec, kind);
+            e = hipMemcpy(d, src, sz * (size_t)nz * rec, kind);
         } else {  // one pitched 2-D copy per slice
             for (int z = 0; z < nz && e == hipSuccess; z++)
-                e = hipMemcpy2D(d + (size_t)z * sz * nbins, sy * rec,
-                                bins + (size_t)z * ny * nx * nbins, (size_t)nx * rec,
+                e = hipMemcpy2D(d + (size_t)z * sz * rec, sy * rec,
+                                src + (size_t)z * ny * nx * rec, (size_t)nx * rec,
                                 (size_t)nx * rec, (size_t)ny, kind);
         }
         if (e != hipSuccess) {
             (void)hipFree(d);
             return hip_fail(e, "hipMemcpy(volume)");
         }
-        g.vol = d;
+        g.vol = reinterpret_cast<float *>(d);
         g.owned = true;
     }
+    g.dtype = dtype;
     g.sy = sy;
     g.sz = sz;
     g.nx = nx;
     g.ny = ny;
     g.nz = nz;
     g.nb = nbins;
+    return VR_OK;
+}
+
+int vr_init_distribution(const float *bins, vr_extent dims, int nbins, int where) {
+    return init_records(bins, dims, nbins, where, VR_DTYPE_F32);
+}
+
+int vr_init_distribution_f16(const void *bins, vr_extent dims, int nbins, int where) {
+    return init_records(bins, dims, nbins, where, VR_DTYPE_F16);
+}
+
+int vr_volume_dtype(void) {
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident");
+    return g.dtype;
+}
+
+// The resident fp32 records narrowed to f16 on the device (k_narrow_f16) into a
+// new library-owned buffer of the same record pitches; the fp32 buffer goes
+// only once the new one is complete, so a failure leaves the volume as it was.
+int vr_convert_f16(void) {
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident");
+    if (g.dtype == VR_DTYPE_F16) return fail(VR_ERR_STATE, "the resident volume is f16 already");
+    if (g.nb != 1 && g.nb != 2 && g.nb != 4 && g.nb != 8 && g.nb != 16 && g.nb != 32)
+        return fail(VR_ERR_UNSUPPORTED, "f16 volumes with %d bins (compiled: 1,2,4,8,16,32)", g.nb);
+    const uint64_t n = g.sz * (uint64_t)g.nz * (uint64_t)g.nb;
+    void *buf = nullptr;
+    VR_HIP(hipMalloc(&buf, n * 2));
+    hipError_t e = vr::launch_narrow_f16(g.vol, buf, n, g.stream);
+    // synchronous, like the statistics bake: a later frame may run on another stream
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return hip_fail(e, "vr_convert_f16(k_narrow_f16)");
+    }
+    release_stats();
+    release_brick();
+    release_axis_copy();
+    g.volume_epoch++;  // the records changed: an order learned on them is not reused
+    if (g.owned) (void)hipFree(g.vol);
+    g.vol = static_cast<float *>(buf);
+    g.owned = true;
+    g.dtype = VR_DTYPE_F16;
     return VR_OK;
 }
 
@@ -1804,6 +1868,17 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
         if (e == hipErrorInvalidValue)
             return fail(VR_ERR_UNSUPPORTED, "codec volumes with %d bins (compiled: 1,2,4,8,16,32)",
                         P.nb);
+    } else if (is_f16()) {
+        // f16 records: one kernel family for every view, on the x rows (no layout
+        // copies, no VR_PATH / VR_SEG / VR_WIDE)
+        if (qm == 7)
+            return fail(VR_ERR_UNSUPPORTED, "method 7 on an f16 volume reads the baked corner "
+                                            "means: basicDataProcessing / vr_bake_stats first");
+        // pixels per wave as the fp32 one-lane march's (fill_params): 16 x 4 blocks
+        // for row-aligned entropy of narrow records, 64-pixel rows otherwise
+        if (!vr::tuning("VR_SEG_MAP"))
+            P.seg_map = P.nb <= 4 && qm == 3 && std::fabs(desc->inv_view[0]) >= 0.95f;
+        e = vr::launch_march_h(g.nb, qm, g.vol, P, nslots, false, g.stream);
     } else {
         // the quad marches of oblique views (methods 1/2/3 on path 0; method 7
         // when its grid is the volume's) read the micro-brick copy
@@ -1877,8 +1952,11 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
     total = bits + nwords;
     hipError_t e = hipMemsetAsync(bits, 0, nwords * 8 + 8, g.stream);
     P.mark = bits;
-    if (e == hipSuccess)
+    if (e == hipSuccess && is_f16()) {  // the counting instance of the f16 march
+        e = vr::launch_march_h(g.nb, desc->query_method, g.vol, P, nslots, true, g.stream);
+    } else if (e == hipSuccess) {
         e = vr::launch_march(g.nb, desc->query_method, g.vol, P, nslots, true, g.stream);
+    }
     if (e == hipSuccess) e = vr::launch_popcount(bits, nwords, total, g.stream);
     unsigned long long u = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&u, total, 8, hipMemcpyDeviceToHost, g.stream);
@@ -1898,7 +1976,7 @@ int64_t vr_footprint_bytes(const vr_render_desc *desc) {
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     if (m <= 3) {
         const int64_t u = vr_count_footprint(desc);
-        return u < 0 ? u : u * (int64_t)g.nb * 4;
+        return u < 0 ? u : u * (int64_t)g.nb * (int64_t)elem_bytes();
     }
     const uint64_t nvox = (uint64_t)P.nx * P.ny * P.nz;
     const uint64_t nwords = (nvox + 63) / 64;

@@ -91,7 +91,8 @@ hipError_t launch_synth_gmm(float *wm, float *sg, const SynthArgs &a, int K, int
 // ---- baked statistics (basicDataProcessing, vr_stats.hip): planes of `plane`
 // floats each in 16 x 2 x 1 bricks of plane pitches psy / psz (plane_index),
 // statistic k+1 (raw) / C = k (codec)
-hipError_t launch_bake_raw(const float *vol, const Params &P, float *out, uint64_t plane,
+// (half: the records are IEEE binary16, vol addresses halves)
+hipError_t launch_bake_raw(const void *vol, bool half, const Params &P, float *out, uint64_t plane,
                            uint64_t psy, uint64_t psz, hipStream_t s);
 hipError_t launch_bake_codec(const Params &P, float *out, uint64_t plane, uint64_t psy,
                              uint64_t psz, hipStream_t s);
@@ -116,6 +117,14 @@ hipError_t launch_plane_axis(const float *src, uint64_t ssy, uint64_t ssz, float
 // of 256 threads; one xor word per workgroup into out (bench read ceiling)
 hipError_t launch_stream_read(const void *buf, uint64_t bytes, uint32_t *out, uint32_t nblocks,
                               hipStream_t s);
+// ---- f16 record volumes (vr_half.hip) ----
+// the per-ray pipelined march over binary16 records in x rows (k_march_pipe_h;
+// methods 1/2/3, nb in 1, 2, 4, 8, 16, 32 -- anything else hipErrorInvalidValue);
+// count: the footprint-marking pass (P.mark)
+hipError_t launch_march_h(int nb, int method, const void *vol, const Params &P, uint32_t nslots,
+                          bool count, hipStream_t s);
+// n floats at src narrowed to n halves at dst (round to nearest even, subnormals kept)
+hipError_t launch_narrow_f16(const float *src, void *dst, uint64_t n, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,

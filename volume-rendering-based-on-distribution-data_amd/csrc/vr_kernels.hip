@@ -15,7 +15,8 @@
 //  k_march_wide / _wq    16- and 32-bin records
 //  k_synth, k_unscatter, k_popcount, k_logcheck
 // Methods 7 and 4/5/6: vr_m7.hip, vr_codec.hip; ray-segmented marches:
-// vr_seg.hip.  K = volumeRender_kernel.cu of the reference.
+// vr_seg.hip; f16 record volumes: vr_half.hip.  K = volumeRender_kernel.cu of
+// the reference.
 #include "vr_device.h"
 #include "vr_internal.h"
 #include "vr_march.h"

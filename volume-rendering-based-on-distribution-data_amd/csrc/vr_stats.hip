@@ -13,6 +13,7 @@
 // the raw volume holds statistic k+1 of voxel (x, y, z), plane 3 method 7's
 // corner mean (the codec volume: 3 planes).
 
+#include "vr_half.h"
 #include "vr_internal.h"
 
 #include <algorithm>
@@ -35,8 +36,10 @@ __device__ __forceinline__ void put_plane(float *__restrict__ out, uint32_t x, u
 // planes hold exactly the per-corner values the march would decode; the
 // entropy's exact logarithm uses the LDS table (both logarithm forms are
 // exact, vr_selftest_logf).
-template <int B>
-__global__ __launch_bounds__(256) void k_bake_raw(const float *__restrict__ vol, Params P,
+// T: the records' element type, float or _Float16 (an f16 volume, vr_half.h:
+// widened exactly, so its planes hold what the f16 march decodes per step)
+template <int B, typename T = float>
+__global__ __launch_bounds__(256) void k_bake_raw(const T *__restrict__ vol, Params P,
                                                   float *__restrict__ out, uint64_t plane,
                                                   uint64_t psy, uint64_t psz) {
     __shared__ LogEnt tab[kLogTabN];
@@ -48,12 +51,19 @@ __global__ __launch_bounds__(256) void k_bake_raw(const float *__restrict__ vol,
     float m, v, e, c;
     if constexpr (B > 0) {
         float p[B];
-        load_rec<B>(vol, off, p);
+        if constexpr (std::is_same<T, float>::value) {
+            load_rec<B>(vol, off, p);
+        } else {
+            RecH<B> h;
+            load_rec_h<B>(vol, off, h);
+            widen_rec<B>(h, p);
+        }
         m = record_stat<B, 1>(p, P.enorm);
         v = record_stat<B, 2>(p, P.enorm);
         e = entropy_p<B>(p, P.enorm, tab);
         c = raw_mean<B>(p);
     } else {
+        static_assert(B > 0 || std::is_same<T, float>::value, "runtime bin counts: fp32 only");
         const float *p = vol + off * (uint64_t)P.nb;
         m = record_stat_rt<1>(p, P.nb, P.enorm);
         v = record_stat_rt<2>(p, P.nb, P.enorm);
@@ -88,11 +98,25 @@ static bool bake_grid(const Params &P, dim3 &grid) {
     return true;
 }
 
-hipError_t launch_bake_raw(const float *vol, const Params &P, float *out, uint64_t plane,
-                           uint64_t psy, uint64_t psz, hipStream_t s) {
+hipError_t launch_bake_raw(const void *vol_any, bool half, const Params &P, float *out,
+                           uint64_t plane, uint64_t psy, uint64_t psz, hipStream_t s) {
     dim3 grid;
     if (!bake_grid(P, grid)) return hipErrorInvalidValue;
     const dim3 block(256);
+    if (half) {
+        const _Float16 *vh = static_cast<const _Float16 *>(vol_any);
+        switch (P.nb) {
+        case 1: hipLaunchKernelGGL((k_bake_raw<1, _Float16>), grid, block, 0, s, vh, P, out, plane, psy, psz); break;
+        case 2: hipLaunchKernelGGL((k_bake_raw<2, _Float16>), grid, block, 0, s, vh, P, out, plane, psy, psz); break;
+        case 4: hipLaunchKernelGGL((k_bake_raw<4, _Float16>), grid, block, 0, s, vh, P, out, plane, psy, psz); break;
+        case 8: hipLaunchKernelGGL((k_bake_raw<8, _Float16>), grid, block, 0, s, vh, P, out, plane, psy, psz); break;
+        case 16: hipLaunchKernelGGL((k_bake_raw<16, _Float16>), grid, block, 0, s, vh, P, out, plane, psy, psz); break;
+        case 32: hipLaunchKernelGGL((k_bake_raw<32, _Float16>), grid, block, 0, s, vh, P, out, plane, psy, psz); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    const float *vol = static_cast<const float *>(vol_any);
     switch (P.nb) {
     case 1: hipLaunchKernelGGL((k_bake_raw<1>), grid, block, 0, s, vol, P, out, plane, psy, psz); break;
     case 2: hipLaunchKernelGGL((k_bake_raw<2>), grid, block, 0, s, vol, P, out, plane, psy, psz); break;
