@@ -193,8 +193,9 @@ int vr_synthesize(vr_extent dims, int nbins, uint64_t seed);
  * vr_bake_stats and with it baked methods 1/2/3/7; tile lists, d_output_f,
  * d_steps, clipped renders; vr_count_footprint, vr_footprint_bytes (U * nbins
  * * 2), vr_stream_read (the real byte size).  Method 7 on an unbaked f16 volume
- * is VR_ERR_UNSUPPORTED (bake first).  Codec, flexible-block and GMM volumes
- * are separate state and always fp32. */
+ * is VR_ERR_UNSUPPORTED (bake first).  Codec and flexible-block volumes are
+ * separate state and always fp32; GMM volumes have their own f16 entry points
+ * (vr_init_gmm_f16 below). */
 #define VR_DTYPE_F32 0
 #define VR_DTYPE_F16 1
 int vr_init_distribution_f16(const void *bins, vr_extent dims, int nbins, int where);
@@ -454,6 +455,45 @@ int vr_init_gmm(const float *wm, const float *sigma, vr_extent dims, int ncomp, 
  * of DESIGN.md 11.1 (a dims-sized volume) directly in HBM. */
 int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int nslices);
 
+/* f16 GMM volumes: the same two planes with IEEE
+ * binary16 elements -- wm 4K bytes and sigma 2K bytes per voxel, same voxel
+ * order, z_base / nslices, slots and `where` values.  f16 -> f32 widening is
+ * exact and the statistic's evaluation order is fixed, so an f16 GMM volume
+ * renders bit-identically to the fp32 volume of the same records widened.
+ * Each slot carries its own element type: an fp32 volume in slot 0 and an f16
+ * volume in slot 1 may be resident together.
+ *
+ * vr_init_gmm_f16: as vr_init_gmm with 2-byte elements.  An adopted pointer
+ * (where == 2) must be aligned to the widest load the march (k_march_gmm_h, 4
+ * components per lane) makes of it: 16 bytes for wm and 8 bytes for sigma
+ * (VR_ERR_ARG otherwise).
+ *
+ * vr_synthesize_gmm_f16: the synthetic volume of vr_synthesize_gmm generated
+ * directly as halves, each value the fp32 generator's rounded to nearest even
+ * (what synthesize-then-narrow gives, without the fp32 planes ever existing).
+ *
+ * vr_convert_gmm_f16: narrows the selected slot's resident fp32 planes to f16
+ * on the device (round to nearest even, subnormals kept) into new
+ * library-owned buffers, then releases the fp32 planes (freed if the library
+ * owned them, forgotten if adopted); peak memory 1.5x the fp32 volume.
+ * VR_ERR_STATE if the slot holds no volume or it is f16 already.
+ *
+ * vr_gmm_dtype: VR_DTYPE_F32 / VR_DTYPE_F16 of the selected slot's volume,
+ * VR_ERR_STATE without one.
+ *
+ * Every call on the selected slot honours its element type: vr_render_gmm
+ * (whole frames and slab launches; queryMethod 1 and 2, anything else
+ * VR_ERR_UNSUPPORTED as for fp32), vr_gmm_count_footprint(_slab), vr_gmm_info,
+ * vr_free_gmm, freeCudaBuffers.  The alive list of a slab chain is the same
+ * 36-byte entry, so slabs of either type may hand rays to each other. */
+int vr_init_gmm_f16(const void *wm, const void *sigma, vr_extent dims, int ncomp, int z_base,
+                    int nslices, int where);
+int vr_synthesize_gmm_f16(vr_extent dims, int ncomp, uint64_t seed, int z_base, int nslices);
+int vr_convert_gmm_f16(void);
+int vr_gmm_dtype(void);
+
+/* dims, component count, resident slices and device pointers of the selected
+ * slot's volume (for an f16 volume, d_wm and d_sigma address halves). */
 int vr_gmm_info(vr_extent *dims, int *ncomp, int *z_base, int *nslices, const float **d_wm,
                 const float **d_sigma);
 int vr_free_gmm(void);
@@ -494,7 +534,7 @@ int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab);
 
 /* U for a whole-volume GMM render: distinct voxels in the union of the
  * footprints of all samples taken (algorithmic bytes = U * 8K for the mean,
- * U * 12K for the variance).  Synchronous. */
+ * U * 12K for the variance; an f16 volume: U * 4K and U * 6K).  Synchronous. */
 int64_t vr_gmm_count_footprint(const vr_render_desc *desc);
 /* U of one slab of a chain (slab as for vr_render_gmm: the samples whose
  * footprint starts in the slab, from its camera rays or its alive list in).

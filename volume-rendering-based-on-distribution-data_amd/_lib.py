@@ -102,6 +102,7 @@ EXPORTS = [
     "vr_gmm_count_footprint", "vr_gmm_count_footprint_slab", "vr_bake_stats", "vr_release_stats", "vr_stats_info",
     "vr_set_tuning", "vr_clear_tuning", "vr_stream_read", "vr_set_layout_budget",
     "vr_layout_info", "vr_init_distribution_f16", "vr_convert_f16", "vr_volume_dtype",
+    "vr_init_gmm_f16", "vr_synthesize_gmm_f16", "vr_convert_gmm_f16", "vr_gmm_dtype",
 ]
 
 _lib = None
@@ -212,6 +213,14 @@ def load() -> ctypes.CDLL:
     L.vr_init_gmm.restype = i32
     L.vr_synthesize_gmm.argtypes = [Extent, i32, ctypes.c_uint64, i32, i32]
     L.vr_synthesize_gmm.restype = i32
+    L.vr_init_gmm_f16.argtypes = [vp, vp, Extent, i32, i32, i32, i32]
+    L.vr_init_gmm_f16.restype = i32
+    L.vr_synthesize_gmm_f16.argtypes = [Extent, i32, ctypes.c_uint64, i32, i32]
+    L.vr_synthesize_gmm_f16.restype = i32
+    L.vr_convert_gmm_f16.argtypes = []
+    L.vr_convert_gmm_f16.restype = i32
+    L.vr_gmm_dtype.argtypes = []
+    L.vr_gmm_dtype.restype = i32
     L.vr_gmm_info.argtypes = [vp] * 6
     L.vr_gmm_info.restype = i32
     L.vr_free_gmm.argtypes = []

@@ -463,12 +463,26 @@ def init_gmm(wm, sigma, dims=None, z_base: int = 0, adopt: bool = False) -> None
     wm: (nzs, ny, nx, K, 2) float32 (w, mu) pairs; sigma: (nzs, ny, nx, K).  numpy
     arrays are copied from the host, torch CUDA tensors device-to-device (or used
     in place with adopt=True).  dims: the whole volume's (X, Y, Z) when only the
-    slices [z_base, z_base + nzs) are given (default: wm's own shape)."""
+    slices [z_base, z_base + nzs) are given (default: wm's own shape).
+
+    numpy.float16 arrays or torch.float16 CUDA tensors become resident as an f16
+    volume (half the bytes, gmm_dtype() == "f16"), which
+    renders bit-identically to the same records widened to float32; both planes
+    must then be float16 (ValueError otherwise; an adopted f16 wm must be 16-byte
+    aligned, sigma 8-byte).  Every other input is taken as float32, as before."""
     L = _lib.load()
     on_device = hasattr(wm, "data_ptr") and getattr(wm, "is_cuda", False)
-    if not on_device:  # lists and other array-likes, as np.asarray takes them
-        wm = np.asarray(wm, dtype=np.float32)
-        sigma = np.asarray(sigma, dtype=np.float32)
+    if on_device:
+        half = str(wm.dtype) == "torch.float16"
+    else:
+        is_h = [isinstance(a, np.ndarray) and a.dtype == np.float16 for a in (wm, sigma)]
+        if is_h[0] != is_h[1]:
+            raise ValueError("wm and sigma must have the same dtype (both float16 or both float32)")
+        half = is_h[0]
+        # lists and other array-likes, as np.asarray takes them
+        wm = np.asarray(wm, dtype=np.float16 if half else np.float32)
+        sigma = np.asarray(sigma, dtype=np.float16 if half else np.float32)
+    init = L.vr_init_gmm_f16 if half else L.vr_init_gmm
     if len(wm.shape) != 5 or int(wm.shape[4]) != 2:
         raise ValueError(f"wm must have shape (nzs, ny, nx, K, 2), got {tuple(wm.shape)}")
     nzs, ny, nx, K = (int(v) for v in wm.shape[:4])
@@ -485,29 +499,47 @@ def init_gmm(wm, sigma, dims=None, z_base: int = 0, adopt: bool = False) -> None
             if t.device != wm.device:
                 raise ValueError(f"{name} is on {t.device}, wm on {wm.device}: both must be on "
                                  "the library's device")
-            if t.dtype != torch.float32:
-                raise ValueError(f"{name} must be float32, got {t.dtype}")
+            if t.dtype != wm.dtype:
+                raise ValueError(f"wm and sigma must have the same dtype, got {wm.dtype} and "
+                                 f"{sigma.dtype}")
+            if t.dtype not in (torch.float32, torch.float16):
+                raise ValueError(f"{name} must be float32 or float16, got {t.dtype}")
             if not t.is_contiguous():
                 raise ValueError(f"{name} must be contiguous (the march reads dense planes)")
-        check(L.vr_init_gmm(_ptr(wm), _ptr(sigma), _extent(dims), K, int(z_base), nzs,
-                            2 if adopt else 1))
+        check(init(_ptr(wm), _ptr(sigma), _extent(dims), K, int(z_base), nzs, 2 if adopt else 1))
         return
-    a = np.ascontiguousarray(np.asarray(wm, dtype=np.float32))
-    b = np.ascontiguousarray(np.asarray(sigma, dtype=np.float32))
-    check(L.vr_init_gmm(a.ctypes.data, b.ctypes.data, _extent(dims), K, int(z_base), nzs, 0))
+    a = np.ascontiguousarray(wm)
+    b = np.ascontiguousarray(sigma)
+    check(init(a.ctypes.data, b.ctypes.data, _extent(dims), K, int(z_base), nzs, 0))
 
 
 def synthesize_gmm(dims, ncomp: int = 16, seed: int = 20261015, z_base: int = 0,
-                   nslices: Optional[int] = None) -> None:
-    """Generate slices [z_base, z_base + nslices) of the seeded synthetic GMM volume in HBM."""
+                   nslices: Optional[int] = None, dtype: str = "f32") -> None:
+    """Generate slices [z_base, z_base + nslices) of the seeded synthetic GMM volume in HBM.
+    dtype "f16": the same values rounded to nearest even, stored as halves."""
+    if dtype not in ("f32", "f16"):
+        raise ValueError(f'dtype must be "f32" or "f16", got {dtype!r}')
     if nslices is None:
         nslices = int(tuple(dims)[2]) - int(z_base)
-    check(_lib.load().vr_synthesize_gmm(_extent(dims), int(ncomp), int(seed), int(z_base),
-                                        int(nslices)))
+    L = _lib.load()
+    synth = L.vr_synthesize_gmm_f16 if dtype == "f16" else L.vr_synthesize_gmm
+    check(synth(_extent(dims), int(ncomp), int(seed), int(z_base), int(nslices)))
+
+
+def convert_gmm_f16() -> None:
+    """Narrow the selected slot's resident float32 GMM planes to f16 on the device
+    (round to nearest even, subnormals kept)."""
+    check(_lib.load().vr_convert_gmm_f16())
+
+
+def gmm_dtype() -> str:
+    """"f32" or "f16": the element type of the selected slot's GMM volume."""
+    return "f16" if check(_lib.load().vr_gmm_dtype()) == _lib.VR_DTYPE_F16 else "f32"
 
 
 def gmm_info():
-    """((X, Y, Z), K, z_base, nslices, wm_ptr, sigma_ptr) of the resident GMM volume"""
+    """((X, Y, Z), K, z_base, nslices, wm_ptr, sigma_ptr) of the resident GMM volume
+    (an f16 volume's pointers address halves)"""
     e = Extent()
     k, zb, ns = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     a, b = ctypes.c_void_p(), ctypes.c_void_p()
@@ -563,6 +595,6 @@ __all__ = [
     "set_stream", "set_tuning", "clear_tuning", "make_desc", "render", "count_footprint", "footprint_bytes", "unscatter_tiles", "last_kernel", "debug_wave_clock", "stream_read", "version",
     "init_gmm", "synthesize_gmm", "gmm_info", "free_gmm", "gmm_select", "gmm_slab", "render_gmm",
     "gmm_count_footprint", "bake_stats", "release_stats", "stats_info", "set_layout_budget",
-    "layout_info", "convert_f16", "volume_dtype",
+    "layout_info", "convert_f16", "volume_dtype", "convert_gmm_f16", "gmm_dtype",
     "VRError", "PAD",
 ]

@@ -61,10 +61,11 @@ struct State {
     unsigned long long *box_check = nullptr;   // vr_debug_box_check (tooling, -DVR_BOX_CHECK builds)
     // GMM volume (config 5, vr_gmm.hip): planes (w, mu)[voxel][K][2] and
     // sigma[voxel][K] of the resident slices [z_base, z_base + nzs) of an
-    // nx x ny x nz volume
+    // nx x ny x nz volume; dtype F16: the planes address halves (section 14)
     struct Gmm {
         float *wm = nullptr, *sg = nullptr;
         bool owned = false;
+        int dtype = VR_DTYPE_F32;
         int nx = 0, ny = 0, nz = 0, K = 0, z_base = 0, nzs = 0;
     } gmm;  // the selected slot's volume (vr_gmm_select)
     // the other slot's volume while not selected (a rank of a two-segment slab
@@ -2153,25 +2154,35 @@ int fill_gmm_params(const vr_render_desc *d, const vr_gmm_slab *slab, vr::Params
     return VR_OK;
 }
 
-}  // namespace
+bool gmm_f16() { return g.gmm.dtype == VR_DTYPE_F16; }
 
-extern "C" {
+// the widest loads k_march_gmm_h makes of a lane's chunk (vr_gmm.hip gmm_gather)
+constexpr size_t kGmmHalfAlignWm = 16, kGmmHalfAlignSigma = 8;
 
-int vr_init_gmm(const float *wm, const float *sigma, vr_extent dims, int ncomp, int z_base,
-                int nslices, int where) {
+// vr_init_gmm / vr_init_gmm_f16: elements of `elem` bytes
+int init_gmm_planes(const void *wm, const void *sigma, vr_extent dims, int ncomp, int z_base,
+                    int nslices, int where, int dtype) {
+    const char *fn = dtype == VR_DTYPE_F16 ? "vr_init_gmm_f16" : "vr_init_gmm";
+    const size_t elem = dtype == VR_DTYPE_F16 ? 2 : sizeof(float);
     int rc = check_gmm_shape(dims, ncomp, z_base, nslices);
     if (rc != VR_OK) return rc;
-    if (!wm || !sigma) return fail(VR_ERR_ARG, "vr_init_gmm: null plane");
-    if (where < 0 || where > 2) return fail(VR_ERR_ARG, "vr_init_gmm: where must be 0, 1 or 2");
+    if (!wm || !sigma) return fail(VR_ERR_ARG, "%s: null plane", fn);
+    if (where < 0 || where > 2) return fail(VR_ERR_ARG, "%s: where must be 0, 1 or 2", fn);
+    if (dtype == VR_DTYPE_F16 && where == 2 &&
+        ((reinterpret_cast<uintptr_t>(wm) & (kGmmHalfAlignWm - 1)) ||
+         (reinterpret_cast<uintptr_t>(sigma) & (kGmmHalfAlignSigma - 1))))
+        return fail(VR_ERR_ARG, "an adopted f16 GMM volume must be aligned to %zu (wm) and %zu "
+                    "(sigma) bytes", kGmmHalfAlignWm, kGmmHalfAlignSigma);
     const uint64_t nvox = (uint64_t)dims.width * dims.height * (uint64_t)nslices;
-    const size_t bwm = nvox * (size_t)ncomp * 8, bsg = nvox * (size_t)ncomp * 4;
+    const size_t bwm = nvox * (size_t)ncomp * 2 * elem, bsg = nvox * (size_t)ncomp * elem;
     release_gmm();
     State::Gmm m;
     m.nx = (int)dims.width; m.ny = (int)dims.height; m.nz = (int)dims.depth;
     m.K = ncomp; m.z_base = z_base; m.nzs = nslices;
+    m.dtype = dtype;
     if (where == 2) {
-        m.wm = const_cast<float *>(wm);
-        m.sg = const_cast<float *>(sigma);
+        m.wm = static_cast<float *>(const_cast<void *>(wm));
+        m.sg = static_cast<float *>(const_cast<void *>(sigma));
         m.owned = false;
     } else {
         hipError_t e = hipMalloc(&m.wm, bwm);
@@ -2182,7 +2193,7 @@ int vr_init_gmm(const float *wm, const float *sigma, vr_extent dims, int ncomp, 
         if (e != hipSuccess) {
             if (m.wm) (void)hipFree(m.wm);
             if (m.sg) (void)hipFree(m.sg);
-            return hip_fail(e, "vr_init_gmm");
+            return hip_fail(e, fn);
         }
         m.owned = true;
     }
@@ -2190,7 +2201,9 @@ int vr_init_gmm(const float *wm, const float *sigma, vr_extent dims, int ncomp, 
     return VR_OK;
 }
 
-int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int nslices) {
+int synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int nslices, int dtype) {
+    const char *fn = dtype == VR_DTYPE_F16 ? "vr_synthesize_gmm_f16" : "vr_synthesize_gmm";
+    const size_t elem = dtype == VR_DTYPE_F16 ? 2 : sizeof(float);
     int rc = check_gmm_shape(dims, ncomp, z_base, nslices);
     if (rc != VR_OK) return rc;
     const int nx = (int)dims.width, ny = (int)dims.height, nz = (int)dims.depth;
@@ -2201,8 +2214,8 @@ int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int 
     release_gmm();
     State::Gmm m;
     float *dgx = nullptr, *dgy = nullptr, *dgz = nullptr;
-    hipError_t e = hipMalloc(&m.wm, nvox * (size_t)ncomp * 8);
-    if (e == hipSuccess) e = hipMalloc(&m.sg, nvox * (size_t)ncomp * 4);
+    hipError_t e = hipMalloc(&m.wm, nvox * (size_t)ncomp * 2 * elem);
+    if (e == hipSuccess) e = hipMalloc(&m.sg, nvox * (size_t)ncomp * elem);
     if (e == hipSuccess) e = hipMalloc(&dgx, gx.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&dgy, gy.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&dgz, gz.size() * 4);
@@ -2212,7 +2225,8 @@ int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int 
     if (e == hipSuccess) {
         a.gx = dgx; a.gy = dgy; a.gz = dgz;
         a.nx = nx; a.ny = ny; a.nz = nz; a.nb = ncomp; a.seed = seed;
-        e = vr::launch_synth_gmm(m.wm, m.sg, a, ncomp, z_base, nslices, g.stream);
+        e = vr::launch_synth_gmm(m.wm, m.sg, dtype == VR_DTYPE_F16, a, ncomp, z_base, nslices,
+                                 g.stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
     if (dgx) (void)hipFree(dgx);
@@ -2221,12 +2235,71 @@ int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int 
     if (e != hipSuccess) {
         if (m.wm) (void)hipFree(m.wm);
         if (m.sg) (void)hipFree(m.sg);
-        return hip_fail(e, "vr_synthesize_gmm");
+        return hip_fail(e, fn);
     }
     m.nx = nx; m.ny = ny; m.nz = nz; m.K = ncomp; m.z_base = z_base; m.nzs = nslices;
     m.owned = true;
+    m.dtype = dtype;
     g.gmm = m;
     return VR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_init_gmm(const float *wm, const float *sigma, vr_extent dims, int ncomp, int z_base,
+                int nslices, int where) {
+    return init_gmm_planes(wm, sigma, dims, ncomp, z_base, nslices, where, VR_DTYPE_F32);
+}
+
+int vr_init_gmm_f16(const void *wm, const void *sigma, vr_extent dims, int ncomp, int z_base,
+                    int nslices, int where) {
+    return init_gmm_planes(wm, sigma, dims, ncomp, z_base, nslices, where, VR_DTYPE_F16);
+}
+
+int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int nslices) {
+    return synthesize_gmm(dims, ncomp, seed, z_base, nslices, VR_DTYPE_F32);
+}
+
+int vr_synthesize_gmm_f16(vr_extent dims, int ncomp, uint64_t seed, int z_base, int nslices) {
+    return synthesize_gmm(dims, ncomp, seed, z_base, nslices, VR_DTYPE_F16);
+}
+
+// The selected slot's fp32 planes narrowed to f16 on the device (k_narrow_f16)
+// into new library-owned buffers; the fp32 planes go only once both new ones
+// are complete, so a failure leaves the volume as it was.
+int vr_convert_gmm_f16(void) {
+    if (!g.gmm.wm) return fail(VR_ERR_STATE, "no GMM volume resident");
+    if (gmm_f16()) return fail(VR_ERR_STATE, "the resident GMM volume is f16 already");
+    const uint64_t n = (uint64_t)g.gmm.nx * g.gmm.ny * (uint64_t)g.gmm.nzs * (uint64_t)g.gmm.K;
+    void *hwm = nullptr, *hsg = nullptr;
+    hipError_t e = hipMalloc(&hwm, n * 4);
+    if (e == hipSuccess) e = hipMalloc(&hsg, n * 2);
+    if (e == hipSuccess) e = vr::launch_narrow_f16(g.gmm.wm, hwm, n * 2, g.stream);
+    if (e == hipSuccess) e = vr::launch_narrow_f16(g.gmm.sg, hsg, n, g.stream);
+    // synchronous, like vr_convert_f16: a later frame may run on another stream
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        if (hwm) (void)hipFree(hwm);
+        if (hsg) (void)hipFree(hsg);
+        return hip_fail(e, "vr_convert_gmm_f16(k_narrow_f16)");
+    }
+    g.volume_epoch++;  // the records changed: an order learned on them is not reused
+    if (g.gmm.owned) {
+        (void)hipFree(g.gmm.wm);
+        (void)hipFree(g.gmm.sg);
+    }
+    g.gmm.wm = static_cast<float *>(hwm);
+    g.gmm.sg = static_cast<float *>(hsg);
+    g.gmm.owned = true;
+    g.gmm.dtype = VR_DTYPE_F16;
+    return VR_OK;
+}
+
+int vr_gmm_dtype(void) {
+    if (!g.gmm.wm) return fail(VR_ERR_STATE, "no GMM volume resident");
+    return g.gmm.dtype;
 }
 
 int vr_gmm_info(vr_extent *dims, int *ncomp, int *z_base, int *nslices, const float **d_wm,
@@ -2271,8 +2344,8 @@ int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
     hipError_t e = slab ? hipMemsetAsync(slab->d_n_rays_out, 0, sizeof(uint32_t), g.stream)
                         : hipSuccess;
     if (e == hipSuccess)
-        e = vr::launch_march_gmm(g.gmm.K, desc->query_method, P, nblocks, false, g.stream);
-    if (e != hipSuccess) return hip_fail(e, "launch(k_march_gmm)");
+        e = vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, false, g.stream);
+    if (e != hipSuccess) return hip_fail(e, gmm_f16() ? "launch(k_march_gmm_h)" : "launch(k_march_gmm)");
     return VR_OK;
 }
 
@@ -2298,7 +2371,7 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
     P.out = nullptr;  // count launch writes no pixels
     P.out_f = nullptr;
     P.out_n = nullptr;
-    if (e == hipSuccess) e = vr::launch_march_gmm(g.gmm.K, desc->query_method, P, nblocks, true, g.stream);
+    if (e == hipSuccess) e = vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, true, g.stream);
     if (e == hipSuccess) e = vr::launch_popcount(bits, nwords, total, g.stream);
     unsigned long long u = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&u, total, 8, hipMemcpyDeviceToHost, g.stream);

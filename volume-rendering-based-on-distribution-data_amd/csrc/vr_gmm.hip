@@ -41,6 +41,17 @@
 // alive to the next slab as an exact state (sums, t, pos, samples taken), so a
 // chain of slab launches in march order reproduces the whole-volume march bit
 // for bit.
+//
+// f16 records: the same two planes with IEEE binary16
+// elements -- 4K bytes of (w, mu) and 2K of sigma per voxel.  k_march_gmm_h is
+// the march above instantiated on the stored type: the corner chunks stay
+// packed, two halves per register, and are widened (exactly) only where the
+// partial sums are formed, so a frame is bit-identical to the fp32 march of
+// the widened records.  Lanes per ray as above, L = K/4: a lane's chunk of a
+// corner is one 16-byte load of (w, mu) and one 8-byte load of sigma.  (L = K/8,
+// two partials per lane added in-lane, measured slower at 1024^3 x 16 in every
+// scene: DESIGN.md 14.3.)
+#include "vr_half.h"
 #include "vr_internal.h"
 #include "vr_march.h"
 
@@ -73,31 +84,73 @@ __device__ __forceinline__ float group_sum(float p) {
     return s;
 }
 
-// this lane's 4 components of one corner record
+// this lane's 4 components of one corner record, in the stored type T; part4()
+// hands them to the statistic as floats
+template <typename T, int M>
+struct GmmPart;
 template <int M>
-struct GmmPart {
+struct GmmPart<float, M> {
     float4 wm[2];                 // (w, mu) of components 4s .. 4s + 3
     float4 sg[1];                 // sigma of the same components (method 2 only)
+    __device__ __forceinline__ void part4(float (&w)[4], float (&mu)[4], float (&sd)[4]) const {
+        const float4 a = wm[0], b = wm[1];
+        w[0] = a.x; mu[0] = a.y; w[1] = a.z; mu[1] = a.w;
+        w[2] = b.x; mu[2] = b.y; w[3] = b.z; mu[3] = b.w;
+        if constexpr (M == 2) {
+            const float4 c = sg[0];
+            sd[0] = c.x; sd[1] = c.y; sd[2] = c.z; sd[3] = c.w;
+        }
+    }
+};
+// binary16: a (w, mu) pair is one register (w the low half), two sigmas another;
+// widened only here, at decode
+template <int M>
+struct GmmPart<_Float16, M> {
+    uint4 wm;                     // (w, mu) of components 4s .. 4s + 3
+    uint2 sg;                     // sigma of the same components (method 2 only)
+    __device__ __forceinline__ void part4(float (&w)[4], float (&mu)[4], float (&sd)[4]) const {
+        const uint32_t p[4] = {wm.x, wm.y, wm.z, wm.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            w[i] = half_bits_to_float(p[i] & 0xFFFFu);
+            mu[i] = half_bits_to_float(p[i] >> 16);
+        }
+        if constexpr (M == 2) {
+            sd[0] = half_bits_to_float(sg.x & 0xFFFFu);
+            sd[1] = half_bits_to_float(sg.x >> 16);
+            sd[2] = half_bits_to_float(sg.y & 0xFFFFu);
+            sd[3] = half_bits_to_float(sg.y >> 16);
+        }
+    }
 };
 
+// the canonical 4-component partials
+__device__ __forceinline__ float gmm_pm(const float (&w)[4], const float (&mu)[4]) {
+    float pm = w[0] * mu[0];
+    pm = __builtin_fmaf(w[1], mu[1], pm);
+    pm = __builtin_fmaf(w[2], mu[2], pm);
+    pm = __builtin_fmaf(w[3], mu[3], pm);
+    return pm;
+}
+__device__ __forceinline__ float gmm_pq(const float (&w)[4], const float (&mu)[4],
+                                        const float (&sd)[4]) {
+    float pq = w[0] * __builtin_fmaf(sd[0], sd[0], mu[0] * mu[0]);
+    pq = __builtin_fmaf(w[1], __builtin_fmaf(sd[1], sd[1], mu[1] * mu[1]), pq);
+    pq = __builtin_fmaf(w[2], __builtin_fmaf(sd[2], sd[2], mu[2] * mu[2]), pq);
+    pq = __builtin_fmaf(w[3], __builtin_fmaf(sd[3], sd[3], mu[3] * mu[3]), pq);
+    return pq;
+}
+
 // statistic of one corner (whole group participates)
-template <int L, int M>
-__device__ __forceinline__ float gmm_stat(const GmmPart<M> &r) {
-    const float4 a = r.wm[0], b = r.wm[1];
-    float pm = a.x * a.y;
-    pm = __builtin_fmaf(a.z, a.w, pm);
-    pm = __builtin_fmaf(b.x, b.y, pm);
-    pm = __builtin_fmaf(b.z, b.w, pm);
-    const float m = group_sum<L>(pm);
+template <int L, int M, typename T>
+__device__ __forceinline__ float gmm_stat(const GmmPart<T, M> &r) {
+    float w[4], mu[4], sd[4];
+    r.part4(w, mu, sd);
+    const float m = group_sum<L>(gmm_pm(w, mu));
     if constexpr (M == 1) {
         return m;
     } else {
-        const float4 c = r.sg[0];
-        float pq = a.x * __builtin_fmaf(c.x, c.x, a.y * a.y);
-        pq = __builtin_fmaf(a.z, __builtin_fmaf(c.y, c.y, a.w * a.w), pq);
-        pq = __builtin_fmaf(b.x, __builtin_fmaf(c.z, c.z, b.y * b.y), pq);
-        pq = __builtin_fmaf(b.z, __builtin_fmaf(c.w, c.w, b.w * b.w), pq);
-        const float q = group_sum<L>(pq);
+        const float q = group_sum<L>(gmm_pq(w, mu, sd));
         const float mm = m * m;
         return (q - mm) * 16.0f;
     }
@@ -160,13 +213,15 @@ __device__ __forceinline__ uint64_t gmm_vox(const Params &P, int x, int y, int z
     return ((uint64_t)(z - P.z_base) * (uint64_t)P.ny + (uint64_t)y) * (uint64_t)P.nx + (uint64_t)x;
 }
 
-// the 8 corner records' 4-component chunks of lane `sub`: one 64-bit base
-// address, the other corners by 32-bit offsets (x pair 0/1 record, y pair
-// 0/1 row, z pair 0/1 slice; a slice is < 2^32 bytes for nx*ny <= 2^26 / K).
+// the 8 corner records' chunks of lane `sub`: one 64-bit base address, the
+// other corners by 32-bit offsets (x pair 0/1 record, y pair 0/1 row, z pair
+// 0/1 slice; a slice is < 2^32 bytes for nx*ny <= 2^26 / K).
 // z is clamped to the resident slices (a slab's discarded last look-ahead).
-template <int K, int M>
+// f16: a lane's chunk is one 16-byte load of (w, mu) and one 8-byte load of
+// sigma, which is the alignment vr_init_gmm_f16 asks of an adopted plane.
+template <typename T, int K, int M>
 __device__ __forceinline__ void gmm_gather(const Params &P, const Foot &f, uint32_t sub,
-                                           GmmPart<M> (&r)[8]) {
+                                           GmmPart<T, M> (&r)[8]) {
     const int zl = P.z_base, zh = P.z_base + P.nzs - 1;
     const int z0 = min(max(f.z0, zl), zh), z1 = min(max(f.z1, zl), zh);
     const uint64_t v = gmm_vox(P, f.x0, f.y0, z0);
@@ -174,17 +229,30 @@ __device__ __forceinline__ void gmm_gather(const Params &P, const Foot &f, uint3
     const uint32_t oy = (uint32_t)(f.y1 - f.y0) * (uint32_t)P.nx;
     const uint32_t oz = (uint32_t)(z1 - z0) * (uint32_t)P.nx * (uint32_t)P.ny;
     const uint32_t off[8] = {0u, ox, oy, ox + oy, oz, oz + ox, oz + oy, oz + oy + ox};
-    const float4 *a = reinterpret_cast<const float4 *>(P.gwm + v * (2u * K)) + sub * 2u;
+    if constexpr (sizeof(T) == 4) {
+        const float4 *a = reinterpret_cast<const float4 *>(P.gwm + v * (2u * K)) + sub * 2u;
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const float4 *q = a + (size_t)off[j] * (K / 2);
-        r[j].wm[0] = q[0];
-        r[j].wm[1] = q[1];
-    }
-    if constexpr (M == 2) {
-        const float4 *b = reinterpret_cast<const float4 *>(P.gsg + v * K) + sub;
+        for (int j = 0; j < 8; j++) {
+            const float4 *q = a + (size_t)off[j] * (K / 2);
+            r[j].wm[0] = q[0];
+            r[j].wm[1] = q[1];
+        }
+        if constexpr (M == 2) {
+            const float4 *b = reinterpret_cast<const float4 *>(P.gsg + v * K) + sub;
 #pragma unroll
-        for (int j = 0; j < 8; j++) r[j].sg[0] = b[(size_t)off[j] * (K / 4)];
+            for (int j = 0; j < 8; j++) r[j].sg[0] = b[(size_t)off[j] * (K / 4)];
+        }
+    } else {
+        const _Float16 *hwm = reinterpret_cast<const _Float16 *>(P.gwm);
+        const uint4 *a = reinterpret_cast<const uint4 *>(hwm + v * (2u * K)) + sub;
+#pragma unroll
+        for (int j = 0; j < 8; j++) r[j].wm = a[(size_t)off[j] * (K / 4)];
+        if constexpr (M == 2) {
+            const _Float16 *hsg = reinterpret_cast<const _Float16 *>(P.gsg);
+            const uint2 *b = reinterpret_cast<const uint2 *>(hsg + v * K) + sub;
+#pragma unroll
+            for (int j = 0; j < 8; j++) r[j].sg = b[(size_t)off[j] * (K / 4)];
+        }
     }
 }
 
@@ -218,11 +286,9 @@ __device__ __forceinline__ void gmm_emit(const Params &P, const GmmState &s, uin
     }
 }
 
-#ifndef VR_GMM_WAVES
-#define VR_GMM_WAVES 1
-#endif
-template <int K, int M, bool COUNT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVES, 8))) void k_march_gmm(Params P) {
+// the march of both kernels, T the stored element
+template <typename T, int K, int M, bool COUNT>
+__device__ __forceinline__ void gmm_march(const Params &P) {
     constexpr int L = K / 4;              // lanes per ray
     constexpr uint32_t R = 64u / L;       // rays in flight per wave
     static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
@@ -270,8 +336,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVE
                         mark_voxel(P.mark, gmm_vox(P, f.x0, f.y1, f.z1)); mark_voxel(P.mark, gmm_vox(P, f.x1, f.y1, f.z1));
                     }
                 }
-                GmmPart<M> rc[8];
-                gmm_gather<K, M>(P, f, sub, rc);
+                GmmPart<T, M> rc[8];
+                gmm_gather<T, K, M>(P, f, sub, rc);
                 float sv[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) sv[j] = gmm_stat<L, M>(rc[j]);
@@ -295,39 +361,72 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVE
     }
 }
 
+#ifndef VR_GMM_WAVES
+#define VR_GMM_WAVES 1
+#endif
 template <int K, int M, bool COUNT>
-static void launch_gmm_km(const Params &P, uint32_t nblocks, hipStream_t s) {
-    hipLaunchKernelGGL((k_march_gmm<K, M, COUNT>), dim3(nblocks), dim3(256), occupancy_lds(P), s, P);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVES, 8))) void k_march_gmm(Params P) {
+    gmm_march<float, K, M, COUNT>(P);
 }
 
-template <int K>
+// Waves per SIMD the register allocation of the f16 march must reach (1: no
+// demand) and may assume (3: a budget of 168 VGPRs; at K = 16 the mean takes 94,
+// the variance 141).  DESIGN.md 14.4: the sweep at 1024^3 x 16.
+#ifndef VR_GMMH_WAVES
+#define VR_GMMH_WAVES 1
+#endif
+#ifndef VR_GMMH_MAXWAVES
+#define VR_GMMH_MAXWAVES 3
+#endif
+template <int K, int M, bool COUNT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMMH_WAVES, VR_GMMH_MAXWAVES))) void k_march_gmm_h(Params P) {
+    gmm_march<_Float16, K, M, COUNT>(P);
+}
+
+template <bool HALF, int K, int M, bool COUNT>
+static void launch_gmm_km(const Params &P, uint32_t nblocks, hipStream_t s) {
+    if constexpr (HALF)
+        hipLaunchKernelGGL((k_march_gmm_h<K, M, COUNT>), dim3(nblocks), dim3(256), occupancy_lds(P), s, P);
+    else
+        hipLaunchKernelGGL((k_march_gmm<K, M, COUNT>), dim3(nblocks), dim3(256), occupancy_lds(P), s, P);
+}
+
+template <bool HALF, int K>
 static hipError_t launch_gmm_k(int method, const Params &P, uint32_t nblocks, bool count,
                                hipStream_t s) {
+    const char *name = HALF ? "k_march_gmm_h" : "k_march_gmm";
     if (count) {  // the samples (and so the footprints) depend on the statistic
-        if (method == 1) launch_gmm_km<K, 1, true>(P, nblocks, s);
-        else if (method == 2) launch_gmm_km<K, 2, true>(P, nblocks, s);
+        if (method == 1) launch_gmm_km<HALF, K, 1, true>(P, nblocks, s);
+        else if (method == 2) launch_gmm_km<HALF, K, 2, true>(P, nblocks, s);
         else return hipErrorInvalidValue;
     } else if (method == 1) {
-        note_kernel("k_march_gmm", K, 1);
-        launch_gmm_km<K, 1, false>(P, nblocks, s);
+        note_kernel(name, K, 1);
+        launch_gmm_km<HALF, K, 1, false>(P, nblocks, s);
     } else if (method == 2) {
-        note_kernel("k_march_gmm", K, 2);
-        launch_gmm_km<K, 2, false>(P, nblocks, s);
+        note_kernel(name, K, 2);
+        launch_gmm_km<HALF, K, 2, false>(P, nblocks, s);
     } else {
         return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-hipError_t launch_march_gmm(int K, int method, const Params &P, uint32_t nblocks, bool count,
-                            hipStream_t s) {
-    if (nblocks == 0) return hipSuccess;
+template <bool HALF>
+static hipError_t launch_gmm_t(int K, int method, const Params &P, uint32_t nblocks, bool count,
+                               hipStream_t s) {
     switch (K) {
-    case 8: return launch_gmm_k<8>(method, P, nblocks, count, s);
-    case 16: return launch_gmm_k<16>(method, P, nblocks, count, s);
-    case 32: return launch_gmm_k<32>(method, P, nblocks, count, s);
+    case 8: return launch_gmm_k<HALF, 8>(method, P, nblocks, count, s);
+    case 16: return launch_gmm_k<HALF, 16>(method, P, nblocks, count, s);
+    case 32: return launch_gmm_k<HALF, 32>(method, P, nblocks, count, s);
     default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_march_gmm(int K, int method, bool half, const Params &P, uint32_t nblocks,
+                            bool count, hipStream_t s) {
+    if (nblocks == 0) return hipSuccess;
+    return half ? launch_gmm_t<true>(K, method, P, nblocks, count, s)
+                : launch_gmm_t<false>(K, method, P, nblocks, count, s);
 }
 
 // ---- synthetic GMM volume ----
@@ -343,7 +442,10 @@ __device__ __forceinline__ uint64_t gmm_hash(uint64_t x) {
     return z ^ (z >> 31);
 }
 
-__global__ __launch_bounds__(256) void k_synth_gmm(float *__restrict__ wm, float *__restrict__ sg,
+// T: the stored element; (T) of a float rounds to nearest even (_Float16:
+// v_cvt_f16_f32, subnormals kept), so the f16 volume is the fp32 one narrowed
+template <typename T>
+__global__ __launch_bounds__(256) void k_synth_gmm(T *__restrict__ wm, T *__restrict__ sg,
                                                    SynthArgs a, int K, int z_base, int nzs) {
     const uint64_t nvox = (uint64_t)a.nx * a.ny * (uint64_t)nzs;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -371,21 +473,25 @@ __global__ __launch_bounds__(256) void k_synth_gmm(float *__restrict__ wm, float
             float mu = (f * 0.8f + 0.1f) + (u - 0.5f) * 0.2f;
             mu = fminf(fmaxf(mu, 0.0f), 1.0f);
             const float sig = ((float)(h & 0xFFFFull) * 0x1p-16f) * 0.05f + 0.005f;
-            wm[(lv * K + k) * 2u] = r / sum;
-            wm[(lv * K + k) * 2u + 1u] = mu;
-            sg[lv * K + k] = sig;
+            wm[(lv * K + k) * 2u] = (T)(r / sum);
+            wm[(lv * K + k) * 2u + 1u] = (T)mu;
+            sg[lv * K + k] = (T)sig;
         }
     }
 }
 
-hipError_t launch_synth_gmm(float *wm, float *sg, const SynthArgs &a, int K, int z_base, int nzs,
-                            hipStream_t s) {
+hipError_t launch_synth_gmm(void *wm, void *sg, bool half, const SynthArgs &a, int K, int z_base,
+                            int nzs, hipStream_t s) {
     const uint64_t nvox = (uint64_t)a.nx * a.ny * (uint64_t)nzs;
     uint64_t blocks = (nvox + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_synth_gmm, dim3((uint32_t)blocks), dim3(256), 0, s, wm, sg, a, K, z_base,
-                       nzs);
+    if (half)
+        hipLaunchKernelGGL(k_synth_gmm<_Float16>, dim3((uint32_t)blocks), dim3(256), 0, s,
+                           static_cast<_Float16 *>(wm), static_cast<_Float16 *>(sg), a, K, z_base, nzs);
+    else
+        hipLaunchKernelGGL(k_synth_gmm<float>, dim3((uint32_t)blocks), dim3(256), 0, s,
+                           static_cast<float *>(wm), static_cast<float *>(sg), a, K, z_base, nzs);
     return hipGetLastError();
 }
 

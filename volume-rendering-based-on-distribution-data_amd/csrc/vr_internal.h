@@ -84,10 +84,11 @@ hipError_t launch_flex_blocks(int nb, int nblk, const float *corner_hist, float4
                               hipStream_t s);
 hipError_t launch_march_flex(int method, const Params &P, uint32_t nslots, hipStream_t s);
 // ---- GMM volumes (config 5, vr_gmm.hip) ----
-hipError_t launch_march_gmm(int K, int method, const Params &P, uint32_t nblocks, bool count,
-                            hipStream_t s);
-hipError_t launch_synth_gmm(float *wm, float *sg, const SynthArgs &a, int K, int z_base, int nzs,
-                            hipStream_t s);
+// half: the planes hold IEEE binary16 (k_march_gmm_h)
+hipError_t launch_march_gmm(int K, int method, bool half, const Params &P, uint32_t nblocks,
+                            bool count, hipStream_t s);
+hipError_t launch_synth_gmm(void *wm, void *sg, bool half, const SynthArgs &a, int K, int z_base,
+                            int nzs, hipStream_t s);
 // ---- baked statistics (basicDataProcessing, vr_stats.hip): planes of `plane`
 // floats each in 16 x 2 x 1 bricks of plane pitches psy / psz (plane_index),
 // statistic k+1 (raw) / C = k (codec)

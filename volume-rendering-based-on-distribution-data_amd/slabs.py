@@ -238,10 +238,14 @@ def period_with_handoff(march_ms, rays_out, owners, world: int, frame_bytes: int
     return (max(r["serial_ms"] for r in rows), max(r["overlap_ms"] for r in rows), rows)
 
 
-def max_slices_for(nx: int, ny: int, ncomp: int, hbm_bytes: float, reserve: float = 0.1) -> int:
+def max_slices_for(nx: int, ny: int, ncomp: int, hbm_bytes: float, reserve: float = 0.1,
+                   dtype: str = "f32") -> int:
     """Largest slab (slices, excluding its halo slice) whose GMM records fit in
-    hbm_bytes with a `reserve` fraction left for frame and alive-list buffers."""
-    per_slice = nx * ny * 12 * ncomp
+    hbm_bytes with a `reserve` fraction left for frame and alive-list buffers.
+    dtype: "f32" records are 12 bytes per component, "f16" records 6."""
+    if dtype not in ("f32", "f16"):
+        raise ValueError(f'dtype must be "f32" or "f16", got {dtype!r}')
+    per_slice = nx * ny * (6 if dtype == "f16" else 12) * ncomp
     return int(hbm_bytes * (1 - reserve) // per_slice) - 1
 
 

@@ -44,6 +44,8 @@ class GmmStream:
 
     wm_host: float32 (nz, ny, nx, K, 2) (w, mu) pairs, sg_host: (nz, ny, nx, K),
     torch CPU tensors (pinned for asynchronous copies; pinned here when not).
+    Both may be float16 instead: the ring buffers are then
+    f16 too, half the bytes cross PCIe, and each slab is marched as an f16 volume.
     slab_slices: slices per streamed slab (each HBM buffer holds one more, the
     halo slice the footprints of the slab's last samples read)."""
 
@@ -51,8 +53,12 @@ class GmmStream:
         import torch
         if tuple(sg_host.shape) != tuple(wm_host.shape[:4]) or wm_host.shape[4] != 2:
             raise ValueError("wm_host must be (nz, ny, nx, K, 2) and sg_host (nz, ny, nx, K)")
-        if wm_host.dtype != torch.float32 or sg_host.dtype != torch.float32:
-            raise ValueError("GMM planes are float32")
+        if wm_host.dtype != sg_host.dtype:
+            raise ValueError(f"wm_host and sg_host must have the same dtype, got {wm_host.dtype} "
+                             f"and {sg_host.dtype}")
+        if wm_host.dtype not in (torch.float32, torch.float16):
+            raise ValueError("GMM planes are float32 or float16")
+        self.elem = 2 if wm_host.dtype == torch.float16 else 4
         self.torch = torch
         self.wm = wm_host if wm_host.is_pinned() else wm_host.pin_memory()
         self.sg = sg_host if sg_host.is_pinned() else sg_host.pin_memory()
@@ -61,15 +67,15 @@ class GmmStream:
         self.S = min(int(slab_slices), nz)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         cap = min(self.S + 1, nz)
-        self.dwm = [torch.empty((cap, ny, nx, K, 2), dtype=torch.float32, device=dev)
+        self.dwm = [torch.empty((cap, ny, nx, K, 2), dtype=wm_host.dtype, device=dev)
                     for _ in range(2)]
-        self.dsg = [torch.empty((cap, ny, nx, K), dtype=torch.float32, device=dev)
+        self.dsg = [torch.empty((cap, ny, nx, K), dtype=wm_host.dtype, device=dev)
                     for _ in range(2)]
         self.copy = torch.cuda.Stream(device=dev)
         self.dev = dev
         self.rays = None
         self.cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.slab_bytes = (ny * nx * K * 12) * cap
+        self.slab_bytes = (ny * nx * K * 3 * self.elem) * cap
 
     def _issue_copy(self, b: int, zb: int, ns: int, free_event, sigma: bool) -> object:
         torch = self.torch
@@ -128,6 +134,6 @@ class GmmStream:
         api.free_gmm()  # the library held an adopted view of a ring buffer
         if n_in != 0:
             raise RuntimeError("the last slab must end every ray")
-        per_voxel = self.K * (12 if sigma else 8)
+        per_voxel = self.K * (3 if sigma else 2) * self.elem
         return {"slabs": len(bounds), "rays_handed_on": handed,
                 "bytes_streamed": sum(ns for _, ns in res) * self.dims[0] * self.dims[1] * per_voxel}
