@@ -126,7 +126,8 @@ def test_tuning_knobs_are_explicit(pkg):
     assert src.count("getenv(") == 1
     i = src.index("getenv(")
     assert src.rfind("#ifdef VR_TUNING", 0, i) > src.rfind("#endif", 0, i)
-    for f in ("vr_kernels.hip", "vr_seg.hip", "vr_gmm.hip", "vr_stats.hip", "vr_flex.hip"):
+    for f in ("vr_kernels.hip", "vr_seg.hip", "vr_gmm.hip", "vr_stats.hip", "vr_flex.hip",
+              "vr_plan.cpp", "vr_m7.hip", "vr_half.hip"):
         assert "getenv(" not in open(os.path.join(ROOT, "volume-rendering-based-on-"
                                                   "distribution-data_amd", "csrc", f)).read()
 

@@ -1,6 +1,6 @@
 """Kernel-choice cliff: frame time over view rotations (tooling).
 
-The march kernel is chosen on the view (vr_api.cpp fill_params): when the
+The march kernel is chosen on the view (csrc/vr_plan.cpp plan_march): when the
 screen x axis runs along the voxel rows (|invViewMatrix[0]| >= threshold) the
 per-ray pipelined march, else the quad-cooperative march.  For the display()
 camera (C:225-246) m00 = cos(ry), so a yaw sweep crosses that threshold.  For

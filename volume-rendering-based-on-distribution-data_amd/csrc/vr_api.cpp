@@ -519,15 +519,6 @@ void device_lds(int &per_cu, int &per_wg) {
     per_wg = wg;
 }
 
-// gather8's 32-bit addressing of a baked plane: pitches and depth fit 24-bit
-// multiplies and the byte offset of every element fits 32 bits (a 1024^3 plane,
-// 2^30 floats, does: the last element sits at 2^32 - 4)
-// a baked plane's index fits the 32-bit form of gather8 (MODE 1: 24-bit
-// multiplies, 32-bit sums): pitches and depth < 2^24, plane < 2^32 floats
-int plane_narrow(uint64_t sy, uint64_t sz, uint64_t nz) {
-    return sy < (1u << 24) && sz < (1u << 24) && nz < (1u << 24) && sz * nz < (1ull << 32);
-}
-
 int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
                 bool for_render = false) {
     if (!d) return fail(VR_ERR_ARG, "null render descriptor");
@@ -596,280 +587,20 @@ int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
     P.out_f = d->d_output_f;
     P.out_n = d->d_steps;
     P.mark = nullptr;
-    // VR_BOX_MAX: per-wave LDS box capacity (tuning / ablation knob; 0 disables staging)
-    P.box_max = vr::kBoxMax;
-    if (const char *e = vr::tuning("VR_BOX_MAX")) {
-        const int v = std::atoi(e);
-        if (v >= 0 && v <= 2048) P.box_max = v;
-    }
-    // VR_WG_PER_CU: cap resident workgroups per CU through the LDS request (tuning knob)
+    // VR_WG_PER_CU / VR_SEG_MAP for the codec and flexible-block launches; the
+    // record marches take theirs, with every other launch knob, from the plan
+    // (plan_input / apply_plan below, vr_plan.cpp)
     P.wg_per_cu = 0;
     if (const char *e = vr::tuning("VR_WG_PER_CU")) {
         const int v = std::atoi(e);
         if (v >= 1 && v <= 32) P.wg_per_cu = v;
     }
-    // Kernel choice (measured at 1024^3 x 8).  When the
-    // screen x axis runs along the volume's voxel rows (|m[0]| ~ 1, e.g. the
-    // runSingleTest view) consecutive lanes read consecutive records and the
-    // per-ray pipelined march (path 2) is fastest for mean and variance; the
-    // log-heavy entropy decode prefers the wave-staged march (path 4), which
-    // decodes every record once per wave-step instead of once per touching
-    // ray.  Oblique views use the quad-cooperative gathers (path 0, B == 8),
-    // which keep every 4-lane group on one contiguous 64-byte run.
-    // VR_PATH overrides (vr_set_tuning): 0 quad, 1 k_march (LDS-staged box /
-    // per-ray), 2 per-ray pipelined, 4 wave-staged rows, 7 ray-segmented
-    // (VR_SEG lanes per ray).
-    const bool along_rows = std::fabs(d->inv_view[0]) >= 0.95f;
-    // (entropy of 1-4 bins: the one-lane pipelined march, round 6 -- 1024^3 x 2
-    // 1080p C0 4.66 -> 3.25 ms, x 4 4.51 -> 4.35 against the wave-staged march;
-    // profiles/r06/knobs/m3_1024x*.log)
-    P.path = along_rows ? (d->query_method == 3 && g.nb >= 8 ? 4 : 2) : 0;
-    // 8-bin entropy of row-aligned views: the LDS-box march with the rolled
-    // LDS-column entropy (k_march<8,3>, 128 VGPRs) beats the wave-staged march:
-    // 1024^3 C0 4.31 -> 3.52 ms, 512^3 3.10 -> 1.63 (round 4,
-    // profiles/r04/variants_1024x8_m3.log, variants_512x8_m3.log).  Rank tile
-    // lists too: cost-dealt 1024^3 C0 lists, max over ranks, k_march vs the
-    // wave-staged march N = 2 1.99 vs 2.52 ms, N = 4 1.52 vs 1.67, N = 8 1.51 vs
-    // 1.51 (round 5, profiles/r05/rank_sim_m3_C0_paths.log)
-    if (along_rows && d->query_method == 3 && g.nb == 8) P.path = 1;
-    // ... and of oblique views of a volume coarse for the frame (>= 4 pixels per
-    // voxel of the x-y face): 512^3 C1 m3 8.32 -> 5.11 ms; at 1024^3 the quad
-    // march stays ahead (8.42 vs 8.61; profiles/r04/variants_*_m3_r4g.log)
-    // (16 and 32 bins too, round 6: 512^3 x 16 C1 m3 8.60 -> 5.56 ms, x 32 15.9 ->
-    // 10.3; at 1024^3 the quad march stays ahead, 9.05 vs 10.3 and 16.9 vs 19.1;
-    // profiles/r06/knobs/wide_*.log, m3_512x32.log)
-    if (!along_rows && d->query_method == 3 && (g.nb == 8 || g.nb == 16 || g.nb == 32) &&
-        !d->d_tile_list &&
-        (uint64_t)d->width * d->height >= 4ull * (uint64_t)g.nx * (uint64_t)g.ny)
-        P.path = 1;
-    P.oblique = along_rows ? 0 : 1;
+    if (const char *e = vr::tuning("VR_SEG_MAP")) P.seg_map = std::atoi(e) != 0;
+    P.oblique = std::fabs(d->inv_view[0]) >= 0.95f ? 0 : 1;
     device_lds(P.lds_cu, P.lds_wg);
-    // Views whose screen x runs along the volume's z or y (|M[8]| / |M[4]| >=
-    // 0.95) march an axis-rows copy of an owned B <= 8 volume with the per-ray
-    // pipelined march (ensure_axis_copy); for the choices below
-    // they count as row-aligned (their x-row seg / quad alternatives read the
-    // x rows across).  VR_ZROWS=0 keeps them oblique.
-    // 8-bin entropy of such views takes the LDS-box march on the x rows instead:
-    // the pipelined march decodes all 8 corners' 64 logarithms per step
-    // unrolled and spills (1024^3 x 8 side view S m3: 18.8 ms; box 3.38, quad
-    // 5.55, wave-staged 5.12; profiles/r06/knobs/side_m3.log)
-    const bool axis_dir = std::fabs(d->inv_view[8]) >= 0.95f || std::fabs(d->inv_view[4]) >= 0.95f;
-    const bool axis_m3 = !along_rows && axis_dir && d->query_method == 3 && g.nb == 8;
-    const char *ez = vr::tuning("VR_ZROWS");
-    P.axis_view = 0;
-    if (!along_rows && !codec && !flex && g.owned && d->query_method >= 1 &&
-        d->query_method <= 3 && (g.nb == 1 || g.nb == 2 || g.nb == 4 || g.nb == 8) &&
-        !axis_m3 && !(ez && std::atoi(ez) == 0))
-        P.axis_view = std::fabs(d->inv_view[8]) >= 0.95f ? 2 : std::fabs(d->inv_view[4]) >= 0.95f ? 1 : 0;
-    const bool row_like = along_rows || P.axis_view != 0;
-    if (P.axis_view) P.path = 2;
-    if (axis_m3 && !codec && !flex) P.path = 1;
-    // Side and top views of 16- and 32-bin records (no axis copy: B <= 8 only)
-    // likewise take the LDS-box march on the x rows instead of the quad march:
-    // 1024^3 x 32 side view m1 13.7 -> 6.9 ms, m3 15.4 -> 7.6, top view m1 7.6 ->
-    // 7.0, m3 15.4 -> 7.5; 1024^3 x 16 side m1 6.7 -> 4.9, m3 8.6 -> 4.4; 512^3 x
-    // 16 side m1 3.7 -> 1.3, m3 8.2 -> 1.9 (profiles/r06/knobs/wide_*.log)
-    if (!along_rows && axis_dir && (g.nb == 16 || g.nb == 32) && !d->d_tile_list &&
-        d->query_method >= 1 && d->query_method <= 3 && !codec && !flex)
-        P.path = 1;
-    // Launches of few rays (a rank's tile list at 4 or 8 GPUs, 1080p) are bound
-    // by the per-ray step chain, not by HBM: there the pipelined ray-segmented
-    // march (2 lanes per ray, next window gathered before this one decodes,
-    // path 7) renders mean / variance row-aligned views faster than the
-    // one-lane march (cost-dealt 1024^3x8 C0 lists, max over ranks: N = 8
-    // 0.217 ms vs 0.265 for plain 4-lane windows, N = 4 0.410 vs 0.44 one-lane);
-    // at 2 GPUs (~1.04 M rays per rank) the one-lane march still wins (0.70 vs
-    // 0.81 ms) (tools/rank_sim.py, tools/gpu_seg4.sh).
-    // VR_SEG_RAYS overrides the ray-count threshold.
-    uint64_t seg_rays = 700000;
-    if (const char *e = vr::tuning("VR_SEG_RAYS")) seg_rays = std::strtoull(e, nullptr, 10);
-    // Views along the volume's z or y (axis-rows copy) split the rays of such
-    // lists the same way, the windows' gathers addressed in the copy
-    // (k_march_segp2_zrows: cost-dealt side-view 1024^3 x 8 lists, max over
-    // ranks, N = 8 0.399 -> 0.247 ms, N = 4 0.543 -> 0.445; the one-lane march's
-    // step chain bound them; profiles/r03/rank_sim_1024x8_S*.log).
-    if (row_like && d->d_tile_list && (d->query_method == 1 || d->query_method == 2) &&
-        (uint64_t)d->n_tiles * vr::kTileW * vr::kTileH <= seg_rays)
-        P.path = 7;
-    // Oblique views of a volume coarse for the frame (>= 4 pixels per voxel of
-    // the x-y face, e.g. 512^3 at 1080p): neighbouring rays share most records,
-    // the launch is bound by the per-ray step chain rather than HBM, and the
-    // pipelined 2-lane segmented march beats the quad march (512^3 x 8 C1: m1
-    // 2.05 -> 1.77 ms, m2 1.87 -> 1.63; at 1024^3, 2 pixels per voxel, the quad
-    // march stays ahead: 3.49 vs 5.23 ms; profiles/r02/paths_512x8.log).
-    if (!row_like && g.nb == 8 && (d->query_method == 1 || d->query_method == 2) &&
-        (uint64_t)d->width * d->height >= 4ull * (uint64_t)g.nx * (uint64_t)g.ny)
-        P.path = 7;
-    // Row-aligned full frames of such a coarse volume: a wave's 64 rays cover
-    // ~16 voxel columns, so staging the wave's footprint box in LDS (path 1,
-    // each record fetched and decoded once per wave) beats the one-lane
-    // pipelined march (512^3 x 8 C0 1080p: m1 1.00 -> 0.88 ms, m2 1.00 -> 0.73;
-    // it loses for entropy, oblique views, 1024^3 and launches of <= 262 K
-    // rays: profiles/r02/paths_coarse_rows.log).
-    // The same holds for 16- and 32-bin records, whose box rows load through the
-    // quad-cooperative gathers (512^3 x 32 C0 1080p m1: box 2.97 ms, quad march
-    // 6.04; profiles/r02/wide_records.log), entropy included: decoding each record
-    // once per wave is what the log-heavy wide decode needs (VR_BOX3=0: quad march).
-    const bool wide3 = (g.nb == 16 || g.nb == 32) && d->query_method == 3 &&
-                       !(vr::tuning("VR_BOX3") && std::atoi(vr::tuning("VR_BOX3")) == 0);
-    // 8-bin mean and variance there take two samples per footprint box
-    // (k_march_duo): 512^3 x 8 C0 m1 0.694 -> 0.623 ms, m2 0.571 -> 0.496; three
-    // or four per box 0.655 / 0.707; at 1024^3 (VR_PATH=1) the doubled boxes lose,
-    // 1.69 -> 2.26 (profiles/r04/variants_*_duo_r4l.log)
-    // Side and top views of such a coarse volume too, on the x rows without the
-    // axis copy (the face across the view is then y-z or x-z): 512^3 x 8 1080p
-    // side view m1 1.14 -> 0.74 ms, m2 1.13 -> 0.55; top view m1 1.08 -> 0.75,
-    // m2 1.09 -> 0.54 (profiles/r06/knobs/side_512x8_m*.log)
-    const uint64_t face = P.axis_view == 2 ? (uint64_t)g.ny * g.nz
-                          : P.axis_view == 1 ? (uint64_t)g.nx * g.nz : (uint64_t)g.nx * g.ny;
-    if (row_like && !d->d_tile_list && (g.nb == 8 || g.nb == 16 || g.nb == 32) &&
-        (d->query_method == 1 || d->query_method == 2 || (wide3 && along_rows)) &&
-        (uint64_t)d->width * d->height > seg_rays &&
-        (uint64_t)d->width * d->height >= 4ull * face) {
-        P.path = 1;
-        P.duo = 2;
-    }
-    // 32-bin records (the reference's own width) are decode-bound at any volume
-    // size, and with a 16x4-pixel block per wave the box decodes each record
-    // once per wave-step instead of once per touching ray: row-aligned full
-    // frames at 1024^3 x 32, 1080p, C0: m1 6.67 -> 6.18 ms, m2 10.42 -> 9.05,
-    // m3 41.0 -> 35.0 (16 bins: no gain; profiles/r03/box_map.log)
-    if (along_rows && !d->d_tile_list && g.nb == 32 && d->query_method >= 1 &&
-        d->query_method <= 3 && (uint64_t)d->width * d->height > seg_rays)
-        P.path = 1;
-    // 16-bin entropy of row-aligned full frames: the box decodes each record
-    // once per wave-step with the rolled LDS-column entropy (round 4): 1024^3 x
-    // 16 C0 m3 12.3 -> 5.6 ms; oblique views keep the quad march (13.7 vs 14.0)
-    // (profiles/r04/variants_1024x16_m3_r4g.log)
-    if (along_rows && !d->d_tile_list && g.nb == 16 && d->query_method == 3 &&
-        (uint64_t)d->width * d->height > seg_rays)
-        P.path = 1;
-    // Mid-size row-aligned full frames of such a coarse volume (more rays than the
-    // small-frame threshold below, fewer than the segmented one: BASELINE config 2,
-    // 256^3 x 4 at 512^2): a round of 4 waves per SIMD whose per-step overheads
-    // dominate, so the box march with four samples per box (k_march_duo) beats the
-    // one-lane march for 4 and 8 bins: 256^3 x 4 C0 m1 0.129 -> 0.105 ms, m2 0.104
-    // -> 0.076; 256^3 x 8 at 512^2 m1 0.271 -> 0.245, m2 0.240 -> 0.144; 384^3 x 4 at
-    // 768^2 m1 0.197 -> 0.198, m2 0.176 -> 0.137; 2 bins lose (m2 0.188 -> 0.213)
-    // (profiles/r04/variants_midsize_duo_r4ad.log)
-    {
-        const uint64_t rays = (uint64_t)d->width * d->height;
-        if (along_rows && !d->d_tile_list && !codec && !flex && (g.nb == 4 || g.nb == 8) &&
-            (d->query_method == 1 || d->query_method == 2) && rays > 131072 &&
-            rays <= seg_rays && rays >= 4ull * (uint64_t)g.nx * (uint64_t)g.ny) {
-            P.path = 1;
-            P.duo = 4;
-        }
-    }
-    // Small full frames (BASELINE configs 1 and 2: 128^3 x 1 at 256^2, 256^3 x 4
-    // at 512^2) cannot fill the GPU with one ray per lane, so the per-ray step
-    // chain sets the time, as for a rank's tile list: the pipelined
-    // ray-segmented march, 4 lanes per ray up to 128 K rays, else 2.  Measured
-    // (profiles/r02/small_frames.log): 128^3 x 1 C0 0.136 -> 0.082 ms, C1
-    // 0.180 -> 0.093; 256^3 x 4 C1 0.224 -> 0.147 (its row-aligned view, 262 K
-    // rays, takes the box march above).  Oblique views
-    // of 8-bin volumes keep the quad march (as for oblique rank lists).
-    int small_seg = 0;
-    {
-        const uint64_t rays = (uint64_t)d->width * d->height;
-        const bool nb_ok = g.nb == 1 || g.nb == 2 || g.nb == 4 || (g.nb == 8 && row_like);
-        const uint64_t limit = row_like ? std::min<uint64_t>(seg_rays, 131072) : seg_rays;
-        if (!d->d_tile_list && !codec && !flex && rays <= limit && nb_ok &&
-            (d->query_method == 1 || d->query_method == 2)) {
-            P.path = 7;
-            // oblique frames up to 400 K rays on 4-lane windows too (round 4, after
-            // the unconditional gathers): 256^3 x 4 C1 at 512^2 0.161 -> 0.135 ms
-            // (profiles/r04/variants_256x4_r4g.log)
-            small_seg = (rays <= 131072 || (!row_like && rays <= 400000)) ? -4 : -2;
-        }
-        // Entropy of such frames with 1, 2 or 4 bins (round 4): the wave-staged
-        // march (row-aligned) and the one-lane march (oblique) lose to 2-lane
-        // windows, and row-aligned coarse frames above 128 K rays to the LDS box:
-        // 128^3 x 1 at 256^2 C0 1.066 -> 0.481 ms, C1 0.988 -> 0.514; 256^3 x 4 at
-        // 512^2 C0 1.600 -> 1.185 (box), C1 2.299 -> 1.707; 256^3 x 2 at 512^2 C0
-        // 1.343 -> 0.783 (box), C1 1.113 -> 1.064 (profiles/r04/variants_midsize_m3_r4ag.log)
-        // Round 6, after the cheaper exact log: 2 and 4 bins take the one-lane
-        // pipelined march instead (256^3 x 4 at 512^2 C0 1.14 -> 0.99 ms, C1 1.66 ->
-        // 1.12; 384^3 x 4 at 768^2 C0 1.84 -> 1.54, C1 2.96 -> 1.65; 256^3 x 2 C0
-        // 0.76 -> 0.68, C1 1.04 -> 0.90); one bin keeps the 2-lane windows (128^3
-        // x 1 C0 0.47 vs 0.51, C1 0.50 vs 0.80; profiles/r06/knobs/m3_*.log)
-        if (!d->d_tile_list && !codec && !flex && d->query_method == 3 && !P.axis_view &&
-            (g.nb == 1 || g.nb == 2 || g.nb == 4) && rays <= seg_rays) {
-            if (g.nb != 1) {
-                P.path = 2;
-            } else if (along_rows && rays > 131072 && rays >= 4ull * (uint64_t)g.nx * (uint64_t)g.ny) {
-                P.path = 1;
-            } else {
-                P.path = 7;
-                small_seg = -2;
-            }
-        }
-    }
-    if (P.path != 2 && P.path != 7) P.axis_view = 0;  // 7: the segmented march reads the copy too
-    if (const char *e = vr::tuning("VR_DUO")) {  // 0 / 1: one sample per box, 2-4: that many
-        const int v = std::atoi(e);
-        if (v >= 0 && v <= 4) P.duo = v;
-    }
-    if (const char *e = vr::tuning("VR_PATH")) {
-        const int v = std::atoi(e);
-        if (v == 0 || v == 1 || v == 2 || v == 4 || v == 7) {
-            P.path = v;
-            P.axis_view = 0;  // a forced path reads the x rows
-        }
-    }
-    // The quad march (path 0: oblique views, B = 8, methods 1-3) of a rank's tile
-    // list of <= 700 K rays (N >= 4 GPUs at 1080p) takes two lanes per ray
-    // (k_march_quad2): such a launch is bound by its longest waves' step chains,
-    // which halve.  Cost-dealt 1024^3 x 8 C1 lists, max over ranks: N = 8
-    // 0.586 -> 0.455 ms, N = 4 0.955 -> 0.880; N = 2 (1 M rays) 1.64 -> 1.68 and
-    // the full frame 3.15 -> 3.35 keep one lane per ray (tools/rank_sim.py,
-    // profiles/r03/rank_sim_1024x8_C1_quad2.log).  VR_QUAD2=0/1 overrides.
-    P.quad2 = d->d_tile_list && (uint64_t)d->n_tiles * vr::kTileW * vr::kTileH <= 700000u;
-    if (const char *e = vr::tuning("VR_QUAD2")) P.quad2 = std::atoi(e) != 0;
     P.wave_clock = g.wave_clock;
     P.box_check = g.box_check;
     P.tile_cost = record;
-    P.seg_lanes = small_seg ? small_seg : -2;  // VR_SEG=S: S lanes per ray, negative = pipelined windows
-    if (const char *e = vr::tuning("VR_SEG")) {
-        const int v = std::atoi(e);
-        if (v == 2 || v == 4 || v == -2 || v == -4) P.seg_lanes = v;
-    }
-    // A wave's rays as a compact pixel block (16 x 4 one lane per ray, (64 / S / 4)
-    // x 4 in S-lane windows) instead of a 64- or 64/S-pixel row: its loads touch
-    // fewer lines per instruction.  Measured per launch kind (tools/bench_variants.py,
-    // tools/rank_sim.py, profiles/r06/segmap/): small full frames on pipelined
-    // windows 128^3 x 1 at 256^2 m1 C0 0.075 -> 0.070 ms, C1 0.078 -> 0.077, m3 C0
-    // 0.490 -> 0.438 (C1 0.493 vs 0.501: kept as rows), 256^3 x 4 at 512^2 m1 C1
-    // 0.143 -> 0.137; row-aligned 2/4-bin entropy on the one-lane march 1024^3 x 2
-    // 1080p C0 3.23 -> 3.03, x 4 4.35 -> 4.16 (oblique: 256^3 x 4 C1 1.13 vs 1.22,
-    // kept as rows).  Also kept as rows: the 8-bin one-lane march (headline 1.342
-    // vs 1.352, side view 1.588 vs 1.628) and the rank lists of records (C0 N = 4
-    // 0.376 vs 0.386, N = 8 0.204 vs 0.219).  VR_SEG_MAP=0/1 overrides.
-    P.seg_map = (!d->d_tile_list && P.path == 7 && P.seg_lanes < 0 &&
-                 (along_rows || d->query_method != 3)) ||
-                (P.path == 2 && P.nb <= 4 && d->query_method == 3 && along_rows && !P.axis_view);
-    if (const char *e = vr::tuning("VR_SEG_MAP")) P.seg_map = std::atoi(e) != 0;
-    // A rank's list at 8 GPUs (<= 400 K rays, 2-lane windows) is bound by the step
-    // chains of its longest tiles: its first 64 slots -- the 8 longest tiles of
-    // every XCD sublist -- take 4 lanes per ray in the same launch
-    // (k_march_seg_head).  Cost-dealt 1024^3 x 8 lists, max over 8 ranks: C0
-    // 0.216 -> 0.202 ms (32 / 96 / 128 slots: 0.204 / 0.204 / 0.207; 8 lanes:
-    // 0.212), side view 0.254 -> 0.249-0.263; N = 4 lists (~520 K rays) gain
-    // nothing (0.380 both) and keep the plain windows
-    // (profiles/r04/rank_sim_C0_head.log, rank_sim_S_head.log).
-    // VR_HEAD=slots (0 = off), VR_HEAD_SEG=-2/-4/-8, VR_HEAD_TAIL=1 (one-lane
-    // tail, k_march_pipe_head) override.
-    P.head_slots = 0;
-    if (d->d_tile_list && P.path == 7 && P.nb == 8 &&
-        (d->query_method == 1 || d->query_method == 2) &&
-        (uint64_t)d->n_tiles * vr::kTileW * vr::kTileH <= 400000u)
-        P.head_slots = 64;
-    P.head_lanes = -4;
-    if (const char *e = vr::tuning("VR_HEAD")) P.head_slots = (uint32_t)std::atoi(e) & ~7u;
-    if (const char *e = vr::tuning("VR_HEAD_SEG")) P.head_lanes = std::atoi(e);
-    P.head_tail = 0;
-    if (const char *e = vr::tuning("VR_HEAD_TAIL")) P.head_tail = std::atoi(e);
-    if (!d->d_tile_list) P.head_slots = 0;
     const uint64_t all = (uint64_t)tiles_x(d->width) * tiles_y(d->height);
     if (d->d_tile_list) {
         nslots = d->n_tiles;
@@ -879,52 +610,6 @@ int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
     }
     P.n_tiles = nslots;
     return VR_OK;
-}
-
-// Kernel of a baked-statistics frame (measured at 512^3 and 1024^3 x 8, 1080p,
-// profiles/r02/baked_paths.log).  A baked step is a few dozen VALU operations
-// and 4 pair loads, so the frame is bound by gather issue and line traffic,
-// not by decode: row-aligned views take the one-lane pipelined march (path 2,
-// 1024^3 C0 0.375 ms); oblique views, whose lanes' loads touch many lines per
-// instruction, split each ray over 4 lanes (path 7, VR_SEG 4: 1024^3 C1 2.02
-// -> 1.32 ms, 1.11 at 4 workgroups per CU).  A deeper look-ahead ring (2-8 steps in flight per lane) was
-// slower everywhere but 512^3 C1 (within 3 %).  VR_PATH (2 / 7) overrides;
-// P.seg_lanes keeps a VR_SEG setting.
-int baked_path(const vr_render_desc *d, vr::Params &P) {
-    // a plane's axis copy (P.plane_axis 1 / 2) makes a side / top view row-aligned
-    const bool along_rows = std::fabs(d->inv_view[0]) >= 0.95f || P.plane_axis == 1 ||
-                            P.plane_axis == 2;
-    int path = along_rows ? 2 : 7;
-    int seg = 4;
-    // A rank's tile list (multi-GPU) has few rays, so its longest step chains
-    // set the time: row-aligned lists split rays too (cost-dealt 1024^3 C0
-    // lists, max over ranks: N = 4 (~520 K rays) pipelined 2-lane windows
-    // 0.149 ms vs 0.185 one-lane, N = 8 (~260 K) 4 lanes 0.105 vs 0.165;
-    // N = 2 stays one-lane, 0.233 vs 0.281; tools/rank_sim.py --baked).
-    if (along_rows && d->d_tile_list) {
-        const uint64_t rays = (uint64_t)d->n_tiles * vr::kTileW * vr::kTileH;
-        if (rays <= 400000) path = 7;
-        else if (rays <= 700000) path = 7, seg = -2;
-    }
-    if (path == 7 && !vr::tuning("VR_SEG")) P.seg_lanes = seg;
-    // compact pixel blocks per wave (fill_params): baked frames gain everywhere
-    // but on row-aligned 4-lane windows (1024^3 x 8 1080p C1 0.844 -> 0.817 ms,
-    // C0 one-lane 0.310 -> 0.295; rank lists C1 N = 8 0.168 -> 0.153, C0 N = 4
-    // 0.133 -> 0.124, C0 N = 8 4-lane 0.093 vs 0.096; profiles/r06/segmap/)
-    P.seg_map = !(along_rows && path == 7 && P.seg_lanes > 0);
-    // oblique full frames of a fine volume (< 4 pixels per voxel of the x-y
-    // face): 4 workgroups per CU, fewer rays' lines in flight per L2 (1024^3
-    // C1 1.28 -> 1.11 ms; 2-3 per CU 1.25, 6 1.19); coarse volumes (512^3:
-    // 0.67 uncapped vs 0.73) and row-aligned views run uncapped
-    if (!along_rows && !d->d_tile_list && P.wg_per_cu == 0 &&
-        (uint64_t)d->width * d->height < 4ull * (uint64_t)P.nx * (uint64_t)P.ny)
-        P.wg_per_cu = 4;
-    if (const char *e = vr::tuning("VR_SEG_MAP")) P.seg_map = std::atoi(e) != 0;
-    if (const char *e = vr::tuning("VR_PATH")) {  // the LDS-box march (1) reads x rows only
-        const int v = std::atoi(e);
-        if (v == 2 || v == 7) path = v;
-    }
-    return path;
 }
 
 // Bakes the statistics planes of the resident raw and codec volumes (whichever
@@ -1791,6 +1476,60 @@ int vr_volume_info(vr_extent *dims, int *nbins, const float **d_bins) {
 
 namespace {
 
+static_assert(vr::kPlanTileRays == vr::kTileW * vr::kTileH && vr::kPlanBoxMax == vr::kBoxMax,
+              "vr_plan.h repeats vr_device.h's tile size and box capacity");
+
+// What plan_march() reads of a frame of methods 1/2/3/7 over the resident record
+// volume (P: fill_params' result, with the clip rectangle applied).
+vr::PlanIn plan_input(const vr_render_desc *d, const vr::Params &P, bool count) {
+    vr::PlanIn in = {};
+    in.m0 = d->inv_view[0];
+    in.m4 = d->inv_view[4];
+    in.m8 = d->inv_view[8];
+    in.W = d->width;
+    in.H = d->height;
+    in.CW = P.CW;
+    in.CH = P.CH;
+    in.tile_list = d->d_tile_list != nullptr;
+    in.n_tiles = d->n_tiles;
+    in.method = d->query_method;
+    // (methods 4/5/6 come here only for their baked planes: the codec volume's)
+    const bool codec = d->query_method >= 4 && d->query_method <= 6;
+    in.nb = P.nb;
+    in.nx = P.nx;
+    in.ny = P.ny;
+    in.nz = P.nz;
+    in.owned = !codec && g.owned;
+    in.f16 = !codec && is_f16();
+    in.baked = (codec ? g.cstats : g.stats) != nullptr;
+    in.plane_sy = codec ? g.cstats_sy : g.stats_sy;
+    in.plane_sz = codec ? g.cstats_sz : g.stats_sz;
+    in.m7x = P.m7x;
+    in.m7y = P.m7y;
+    in.m7z = P.m7z;
+    in.count = count;
+    in.tuning = vr::tuning;
+    return in;
+}
+
+// The plan's launch knobs into the Params the kernels (and, for the host-only
+// fields path / duo / quad2 / axis_view, nobody) read.
+void apply_plan(const vr::MarchPlan &pl, vr::Params &P) {
+    P.path = pl.path;
+    P.duo = pl.duo;
+    P.quad2 = pl.quad2;
+    P.axis_view = pl.axis;
+    P.plane_axis = pl.plane_axis;
+    P.seg_lanes = pl.seg_lanes;
+    P.seg_map = pl.seg_map;
+    P.wq_map = pl.wq_map;
+    P.head_slots = pl.head_slots;
+    P.head_lanes = pl.head_lanes;
+    P.head_tail = pl.head_tail;
+    P.box_max = pl.box_max;
+    P.wg_per_cu = pl.wg_per_cu;
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -1809,103 +1548,81 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
         if (P.CW == 0 || P.CH == 0) return VR_OK;
         P.tile_cost = nullptr;
     }
-    // VR_DRY (tooling: tools/host_cost.py): the host work of a frame without its
-    // launch, to time what a frame costs the issuing thread
-    if (const char *e = vr::tuning("VR_DRY"))
-        if (std::atoi(e) != 0) return VR_OK;
+    // VR_DRY (tooling: tools/host_cost.py): the host work of a frame (parameters
+    // and the kernel choice) without its layout copies and its launch, to time
+    // what a frame costs the issuing thread
+    const char *ed = vr::tuning("VR_DRY");
+    const bool dry = ed && std::atoi(ed) != 0;
     hipError_t e;
     const int qm = desc->query_method;
-    const float *baked = (qm >= 1 && qm <= 3 && g.stats)   ? g.stats + (uint64_t)(qm - 1) * g.stats_plane
-                         : (qm >= 4 && qm <= 6 && g.cstats) ? g.cstats + (uint64_t)(qm - 4) * g.cstats_plane
-                                                            : nullptr;
-    if (qm == 7 && g.stats) {
-        // method 7 from the baked corner means (plane 3): the same corner cache
-        // and double lerps (K:395-480), 4 bytes per corner refresh
-        P.nb = 1;
-        P.sy = g.stats_sy;
-        P.sz = g.stats_sz;
-        e = vr::launch_march(1, -7, g.stats + 3 * g.stats_plane, P, nslots, false, g.stream);
-    } else if (baked) {
-        // one float per corner voxel, the same filter and composite (vr_stats.hip),
-        // addressed in the planes' bricks
-        P.nb = 1;
-        P.sy = qm <= 3 ? g.stats_sy : g.cstats_sy;
-        P.sz = qm <= 3 ? g.stats_sz : g.cstats_sz;
-        // side / top views of the raw planes: the method's plane with the view's
-        // axis in the brick rows (ensure_plane_copy), marched as row-aligned
-        P.plane_axis = 0;
-        if (qm <= 3 && std::fabs(desc->inv_view[0]) < 0.95f) {
-            int ax = std::fabs(desc->inv_view[8]) >= 0.95f ? 2
-                         : std::fabs(desc->inv_view[4]) >= 0.95f ? 1 : 0;
-            // oblique views: the 8 x 2 x 2 brick copy (axis 3)
-            if (!ax) ax = 3;
-            if (ensure_plane_copy(qm - 1, ax)) {
-                const State::PlaneCopy &c = g.pcopy[ax - 1][qm - 1];
-                baked = c.buf;
-                P.sy = c.sy;
-                P.sz = c.sz;
-                P.plane_axis = ax;
-            }
-        }
-        P.path = baked_path(desc, P);
-        // method 0: the 32-bit plane index (MODE 1), or a plane copy's MODE 4 / 5
-        // (32-bit in-slice offsets, 64-bit slice offsets: ensure_plane_copy keeps
-        // a slice < 2^32 floats, so a copy never needs -1, which reads x rows);
-        // method -1: x-row planes too large for 32-bit indices (MODE 2).
-        // VR_PLANE_WIDE=1 (tests) sends every x-row plane to -1.
-        const char *ew = vr::tuning("VR_PLANE_WIDE");
-        const bool wide = ew && std::atoi(ew) != 0;
-        const bool narrow = P.plane_axis != 0 || (!wide && plane_narrow(P.sy, P.sz, (uint64_t)P.nz));
-        e = vr::launch_march(1, narrow ? 0 : -1, baked, P, nslots, false, g.stream);
-    } else if (is_flex_method(desc->query_method)) {
-        e = vr::launch_march_flex(desc->query_method, P, nslots, g.stream);
-    } else if (desc->query_method >= 4 && desc->query_method <= 6) {
+    if (is_flex_method(qm)) {
+        if (dry) return VR_OK;
+        e = vr::launch_march_flex(qm, P, nslots, g.stream);
+    } else if (qm >= 4 && qm <= 6 && !g.cstats) {
+        if (dry) return VR_OK;
         // the one-lane codec march of a row-aligned view: a 16x4 pixel block per
         // wave (1024^3 x 8 1080p C0 m4 2.91 -> 2.88 ms, m5 5.26 -> 5.17, m6 7.07 ->
         // 6.90; profiles/r06/segmap/codec_*.log); VR_CODEC_MAP=0/1 overrides
         P.seg_map = std::fabs(desc->inv_view[0]) >= 0.95f;
         if (const char *em = vr::tuning("VR_CODEC_MAP")) P.seg_map = std::atoi(em) != 0;
-        e = vr::launch_march_codec(P.nb, desc->query_method, P, nslots, false, g.stream);
+        e = vr::launch_march_codec(P.nb, qm, P, nslots, false, g.stream);
         if (e == hipErrorInvalidValue)
             return fail(VR_ERR_UNSUPPORTED, "codec volumes with %d bins (compiled: 1,2,4,8,16,32)",
                         P.nb);
-    } else if (is_f16()) {
-        // f16 records: one kernel family for every view, on the x rows (no layout
-        // copies, no VR_PATH / VR_SEG / VR_WIDE)
-        if (qm == 7)
+    } else {
+        // records (fp32 / f16) and baked planes: vr_plan.cpp chooses the march
+        if (qm == 7 && is_f16() && !g.stats)
             return fail(VR_ERR_UNSUPPORTED, "method 7 on an f16 volume reads the baked corner "
                                             "means: basicDataProcessing / vr_bake_stats first");
-        // pixels per wave as the fp32 one-lane march's (fill_params): 16 x 4 blocks
-        // for row-aligned entropy of narrow records, 64-pixel rows otherwise
-        if (!vr::tuning("VR_SEG_MAP"))
-            P.seg_map = P.nb <= 4 && qm == 3 && std::fabs(desc->inv_view[0]) >= 0.95f;
-        e = vr::launch_march_h(g.nb, qm, g.vol, P, nslots, false, g.stream);
-    } else {
-        // the quad marches of oblique views (methods 1/2/3 on path 0; method 7
-        // when its grid is the volume's) read the micro-brick copy
-        const char *eq = vr::tuning("VR_M7_QUAD");
-        const bool m7_quad = qm == 7 && P.oblique && P.m7x == P.nx && P.m7y == P.ny &&
-                             P.m7z == P.nz && !(eq && std::atoi(eq) == 0);
-        // views whose screen x runs along the volume's z or y read that axis'
-        // rows copy with the per-ray pipelined march (fill_params); if the copy
-        // cannot be made (HBM), the oblique view's march on the x rows / bricks
-        if (P.axis_view && !ensure_axis_copy(P.axis_view)) {
-            P.axis_view = 0;
-            P.path = 0;
+        vr::PlanIn in = plan_input(desc, P, false);
+        vr::MarchPlan pl = vr::plan_march(in);
+        if (dry) return VR_OK;
+        // the layout copy the plan marches; if it cannot be made (HBM), the plan
+        // without it
+        while (pl.layout != vr::kLayoutNone) {
+            const bool made = pl.layout == vr::kLayoutAxis    ? ensure_axis_copy(pl.axis)
+                              : pl.layout == vr::kLayoutBrick ? ensure_brick()
+                                                              : ensure_plane_copy(qm - 1, pl.plane_axis);
+            if (made) break;
+            in.denied |= pl.layout;
+            pl = vr::plan_march(in);
         }
-        if (P.axis_view) {
-            const State::AxisCopy &c = g.acopy[P.axis_view - 1];
+        apply_plan(pl, P);
+        const void *vol = g.vol;
+        if (pl.method == -7) {  // the baked corner means (plane 3)
+            vol = g.stats + 3 * g.stats_plane;
+            P.nb = 1;
+            P.sy = g.stats_sy;
+            P.sz = g.stats_sz;
+        } else if (pl.method <= 0) {
+            // the method's baked plane, addressed in its bricks, or its copy for the view
+            P.nb = 1;
+            if (pl.plane_axis) {
+                const State::PlaneCopy &c = g.pcopy[pl.plane_axis - 1][qm - 1];
+                vol = c.buf;
+                P.sy = c.sy;
+                P.sz = c.sz;
+            } else if (qm <= 3) {
+                vol = g.stats + (uint64_t)(qm - 1) * g.stats_plane;
+                P.sy = g.stats_sy;
+                P.sz = g.stats_sz;
+            } else {
+                vol = g.cstats + (uint64_t)(qm - 4) * g.cstats_plane;
+                P.sy = g.cstats_sy;
+                P.sz = g.cstats_sz;
+            }
+        } else if (pl.axis) {
+            const State::AxisCopy &c = g.acopy[pl.axis - 1];
             P.avol = c.buf;
             P.asx = c.sx;
             P.asy = c.sy;
             P.asz = c.sz;
-        } else if (g.nb == 8 && ((P.path == 0 && qm >= 1 && qm <= 3) || m7_quad) &&
-                   ensure_brick()) {
+        } else if (pl.brick) {
             P.bvol = g.brick;
             P.bsy = g.bsy;
             P.bsz = g.bsz;
         }
-        e = vr::launch_march(g.nb, desc->query_method, g.vol, P, nslots, false, g.stream);
+        e = vr::launch_plan(pl, vol, P, nslots, g.stream);
     }
     if (e != hipSuccess) return hip_fail(e, "launch(k_march)");
     if (P.tile_cost) g.cost_recorded = true;
@@ -1953,10 +1670,10 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
     total = bits + nwords;
     hipError_t e = hipMemsetAsync(bits, 0, nwords * 8 + 8, g.stream);
     P.mark = bits;
-    if (e == hipSuccess && is_f16()) {  // the counting instance of the f16 march
-        e = vr::launch_march_h(g.nb, desc->query_method, g.vol, P, nslots, true, g.stream);
-    } else if (e == hipSuccess) {
-        e = vr::launch_march(g.nb, desc->query_method, g.vol, P, nslots, true, g.stream);
+    if (e == hipSuccess) {  // the counting instance of the LDS-box march (f16: of the one-lane march)
+        const vr::MarchPlan pl = vr::plan_march(plan_input(desc, P, true));
+        apply_plan(pl, P);
+        e = vr::launch_plan(pl, g.vol, P, nslots, g.stream);
     }
     if (e == hipSuccess) e = vr::launch_popcount(bits, nwords, total, g.stream);
     unsigned long long u = 0;

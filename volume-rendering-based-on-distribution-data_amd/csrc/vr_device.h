@@ -47,7 +47,7 @@ struct Params {
     int wg_per_cu;               // occupancy cap through the LDS request (0 = none)
     int lds_cu, lds_wg;          // LDS bytes per CU / per workgroup (device attributes)
     int oblique;                 // view's screen x does not run along voxel rows
-    int path;                    // kernel variant (vr_api.cpp fill_params)
+    int path;                    // kernel variant (host-only: vr_plan.cpp MarchPlan::path)
     // 2x2 (x, y) micro-brick copy of the 8-bin records for the quad marches of
     // oblique views (nullptr: none), bsy / bsz its brick-row / slice pitches
     // in records (brick_index); the launch passes it as vol with sy / sz = bsy / bsz
@@ -58,7 +58,7 @@ struct Params {
     // (axis_copy_strides); the launch passes it as vol with sx / sy / sz = asx / asy / asz
     const float *avol;
     uint64_t asx, asy, asz;
-    int axis_view;               // host dispatch: 1 / 2 = the view runs along y / z (fill_params)
+    int axis_view;               // host-only: 1 / 2 = the march reads the y- / z-rows copy (MarchPlan::axis)
     uint64_t sx;                 // record stride of x (gather MODE 3 only; 1 in x rows)
     // fractal/template codec (methods 4/5/6): codebook int4 per voxel, templates
     // [ntpl][nb], (bin, value) errors [voxel][err_slots]

@@ -220,40 +220,40 @@ __global__ __launch_bounds__(256) void k_narrow_f16(const float *__restrict__ sr
 }
 
 template <int B, bool COUNT>
-static hipError_t march_h_b(int method, const _Float16 *vol, const Params &P, uint32_t nslots,
-                            hipStream_t s) {
+static hipError_t march_h_b(const MarchPlan &pl, const _Float16 *vol, const Params &P,
+                            uint32_t nslots, hipStream_t s) {
     const dim3 grid(nslots), block(256);
-    if (!COUNT) note_kernel("k_march_pipe_h", B, method);
-    switch (method) {
-    case 1: hipLaunchKernelGGL((k_march_pipe_h<B, 1, COUNT>), grid, block, occupancy_lds(P), s, vol, P); break;
-    case 2: hipLaunchKernelGGL((k_march_pipe_h<B, 2, COUNT>), grid, block, occupancy_lds(P), s, vol, P); break;
+    const size_t lds = cap_lds(P, pl.cap);
+    switch (pl.method) {
+    case 1: hipLaunchKernelGGL((k_march_pipe_h<B, 1, COUNT>), grid, block, lds, s, vol, P); break;
+    case 2: hipLaunchKernelGGL((k_march_pipe_h<B, 2, COUNT>), grid, block, lds, s, vol, P); break;
     // (the entropy march's LDS columns and table are part of the request)
-    case 3: hipLaunchKernelGGL((k_march_pipe_h<B, 3, COUNT>), grid, block, cap_lds(P, P.wg_per_cu, sizeof(EntropyLds<B>)), s, vol, P); break;
+    case 3: hipLaunchKernelGGL((k_march_pipe_h<B, 3, COUNT>), grid, block, cap_lds(P, pl.cap, sizeof(EntropyLds<B>)), s, vol, P); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
 template <bool COUNT>
-static hipError_t march_h_dispatch(int nb, int method, const _Float16 *vol, const Params &P,
+static hipError_t march_h_dispatch(const MarchPlan &pl, const _Float16 *vol, const Params &P,
                                    uint32_t nslots, hipStream_t s) {
-    switch (nb) {
-    case 1: return march_h_b<1, COUNT>(method, vol, P, nslots, s);
-    case 2: return march_h_b<2, COUNT>(method, vol, P, nslots, s);
-    case 4: return march_h_b<4, COUNT>(method, vol, P, nslots, s);
-    case 8: return march_h_b<8, COUNT>(method, vol, P, nslots, s);
-    case 16: return march_h_b<16, COUNT>(method, vol, P, nslots, s);
-    case 32: return march_h_b<32, COUNT>(method, vol, P, nslots, s);
+    switch (pl.B) {
+    case 1: return march_h_b<1, COUNT>(pl, vol, P, nslots, s);
+    case 2: return march_h_b<2, COUNT>(pl, vol, P, nslots, s);
+    case 4: return march_h_b<4, COUNT>(pl, vol, P, nslots, s);
+    case 8: return march_h_b<8, COUNT>(pl, vol, P, nslots, s);
+    case 16: return march_h_b<16, COUNT>(pl, vol, P, nslots, s);
+    case 32: return march_h_b<32, COUNT>(pl, vol, P, nslots, s);
     default: return hipErrorInvalidValue;  // no runtime-B path for f16
     }
 }
 
-hipError_t launch_march_h(int nb, int method, const void *vol, const Params &P, uint32_t nslots,
-                          bool count, hipStream_t s) {
-    if (nslots == 0) return hipSuccess;
+// Kind::PipeH of the plan; pl.count: the footprint-marking pass (P.mark)
+hipError_t launch_march_h(const MarchPlan &pl, const void *vol, const Params &P, uint32_t nslots,
+                          hipStream_t s) {
     const _Float16 *v = static_cast<const _Float16 *>(vol);
-    return count ? march_h_dispatch<true>(nb, method, v, P, nslots, s)
-                 : march_h_dispatch<false>(nb, method, v, P, nslots, s);
+    return pl.count ? march_h_dispatch<true>(pl, v, P, nslots, s)
+                    : march_h_dispatch<false>(pl, v, P, nslots, s);
 }
 
 hipError_t launch_narrow_f16(const float *src, void *dst, uint64_t n, hipStream_t s) {

@@ -1,11 +1,13 @@
-// vr_internal.h -- declarations shared by the kernels (vr_kernels.hip) and the
-// host-side library state / C-ABI (vr_api.cpp).  Not a public header.
+// vr_internal.h -- declarations shared by the kernels and their launchers (*.hip)
+// and the host-side library state / C-ABI (vr_api.cpp).  The kernel choice of
+// the record marches is vr_plan.h's.  Not a public header.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vr_device.h"
+#include "vr_plan.h"
 
 namespace vr {
 
@@ -33,18 +35,26 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 // records an error for vr_last_error() (vr_api.cpp); returns status
 int record_error(int status, const char *msg);
 
-hipError_t launch_march(int nb, int method, const float *vol, const Params &P,
-                        uint32_t nslots, bool count, hipStream_t s);
-// method 7 (vr_m7.hip; -7: over the baked corner means); launch_march routes to it
-hipError_t launch_march_m7(int nb, int method, const float *vol, const Params &P,
+// Launches the march a plan names (vr_plan.h: plan_march() is the only place
+// that chooses a kernel; the launchers switch on the plan and decide nothing).
+// vol: the records or baked plane the plan's kernel reads (halves for
+// Kind::PipeH); the layout copies travel in P (bvol, avol).  A plan that names
+// an instance that is not compiled returns hipErrorInvalidValue.  A
+// non-counting launch records the plan's kernel name for vr_last_kernel().
+hipError_t launch_plan(const MarchPlan &plan, const void *vol, const Params &P, uint32_t nslots,
+                       hipStream_t s);
+// launch_plan's per-file switches: method 7 (vr_m7.hip; -7: over the baked corner
+// means), the ray-segmented marches (vr_seg.hip), f16 records (vr_half.hip)
+hipError_t launch_march_m7(const MarchPlan &plan, const float *vol, const Params &P,
                            uint32_t nslots, hipStream_t s);
-// name of the march kernel the last non-counting launch_march() chose
+hipError_t launch_march_seg(const MarchPlan &plan, const float *vol, const Params &P,
+                            uint32_t nslots, hipStream_t s);
+hipError_t launch_march_h(const MarchPlan &plan, const void *vol, const Params &P,
+                          uint32_t nslots, hipStream_t s);
+// name of the march kernel the last non-counting launch ran (launch_plan: the
+// plan's plan_kernel_name; the codec, flexible-block and GMM launchers: note_kernel)
 const char *last_march_kernel();
 void note_kernel(const char *kind, int B, int method);
-// ray-segmented march (vr_seg.hip): S lanes per ray; false if (B, S) has no
-// specialisation
-bool launch_march_seg(int nb, int method, int S, const float *vol, const Params &P,
-                      uint32_t nslots, hipStream_t s, hipError_t &err);
 // tuning knob `key` set through vr_set_tuning (nullptr if unset); a -DVR_TUNING
 // build falls back to the environment.  The default build never reads it.
 const char *tuning(const char *key);
@@ -118,12 +128,9 @@ hipError_t launch_plane_axis(const float *src, uint64_t ssy, uint64_t ssz, float
 // of 256 threads; one xor word per workgroup into out (bench read ceiling)
 hipError_t launch_stream_read(const void *buf, uint64_t bytes, uint32_t *out, uint32_t nblocks,
                               hipStream_t s);
-// ---- f16 record volumes (vr_half.hip) ----
-// the per-ray pipelined march over binary16 records in x rows (k_march_pipe_h;
-// methods 1/2/3, nb in 1, 2, 4, 8, 16, 32 -- anything else hipErrorInvalidValue);
-// count: the footprint-marking pass (P.mark)
-hipError_t launch_march_h(int nb, int method, const void *vol, const Params &P, uint32_t nslots,
-                          bool count, hipStream_t s);
+// ---- f16 record volumes (vr_half.hip): the per-ray
+// pipelined march over binary16 records in x rows (k_march_pipe_h; methods 1/2/3,
+// nb in 1, 2, 4, 8, 16, 32), launch_march_h above ----
 // n floats at src narrowed to n halves at dst (round to nearest even, subnormals kept)
 hipError_t launch_narrow_f16(const float *src, void *dst, uint64_t n, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);

@@ -1,5 +1,6 @@
 // vr_kernels.hip -- gfx950 marches of methods 1/2/3 (the d_render path,
-// K:272-717) and the kernel choice between them (march_b).  One 64x4-pixel
+// K:272-717) and launch_plan, which launches the march a plan names (the
+// choice between them is vr_plan.cpp's plan_march).  One 64x4-pixel
 // tile per 256-thread workgroup, XCD-aware tile order; per step the statistic
 // is decoded from the 8 corner distribution records and blended with the
 // texture unit's 8-bit filter weights.
@@ -1420,244 +1421,203 @@ hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s) {
 }
 
 // ------------------------------ launchers ---------------------------------
+// Switches on the plan (vr_plan.cpp chose; nothing is decided here).  A plan
+// that names an instance that is not compiled returns hipErrorInvalidValue.
 
+#define VR_L(K, LDS, V, Q) hipLaunchKernelGGL((K), grid, block, LDS, s, V, Q)
 
-template <int B, bool COUNT>
-static hipError_t march_b(int method, const float *vol, Params P, uint32_t nslots,
-                          hipStream_t s) {
+// the marches of this file for records of B bins (0: runtime bin count)
+template <int B>
+static hipError_t launch_b(const MarchPlan &pl, const float *vol, const Params &P, uint32_t nslots,
+                           hipStream_t s) {
     const dim3 grid(nslots), block(256);
-    // one f32 box slice of box_max voxels per wave (4 waves); a larger request
-    // caps the workgroups resident per CU (160 KiB of LDS per CU)
-    // (+ the log table and the record columns of the wide entropy march, k_march)
-    const size_t lds = cap_lds(P, P.wg_per_cu, B > 0 ? (size_t)P.box_max * 4u * sizeof(float) +
-                                                   (B >= 8 && method == 3 ? kLogTabN * sizeof(LogEnt) + 4u * 64u * B * sizeof(float) : 0) : 0);
-    if constexpr (!COUNT && B > 0 && B <= 8) {
-        if (P.path == 7) {
-            hipError_t err = hipSuccess;
-            if (launch_march_seg(B, method, P.seg_lanes, vol, P, nslots, s, err)) return err;
-            P.path = 2;
-        }
-        if (B == 8 && P.path == 0 && method >= 1 && method <= 3) {
-            note_kernel(P.bvol ? "k_march_quad_brick" : "k_march_quad", B, method);
-            // The quad march uses no LDS; an LDS request caps it at 2 workgroups
-            // (2 waves per SIMD) per CU, which trims the oblique view's line
-            // re-reads: 1024^3x8 C1 3.73 -> 3.52 ms (3 per CU by registers, 1 per
-            // CU 3.91).  VR_WG_PER_CU overrides.
-            // A rank's tile list of <= 400 K rays (8 GPUs at 1080p) runs at 1 per
-            // CU: its tiles are scattered over the frame, and fewer rays in flight
-            // re-read fewer lines (cost-dealt C1 lists, max over 8 ranks: 0.71 ->
-            // 0.59 ms; 3 per CU 0.68; tools/rank_sim.py)
-            const int qcap = P.wg_per_cu > 0 ? P.wg_per_cu
-                             : (P.tile_list && (uint64_t)nslots * 256u <= 400000u) ? 1 : 2;
-            // entropy: the log table (qc_group) at the front
-            const size_t qlds = cap_lds(P, qcap, method == 3 ? kLogTabN * sizeof(LogEnt) : 0);
-            if (P.quad2) {  // two lanes per ray, two workgroups per tile
-                note_kernel(P.bvol ? "k_march_quad2_brick" : "k_march_quad2", B, method);
-                const dim3 grid2(((nslots + 7u) / 8u) * 16u);
-                Params Q = P;
-                if (P.bvol) {
-                    Q.sy = P.bsy;
-                    Q.sz = P.bsz;
+    const int method = pl.method;
+    constexpr bool kNarrow = B > 0 && B <= 8;
+    // the log table (entropy) and, for the rolled LDS-column entropy, a record
+    // column per lane
+    constexpr size_t kTab = kLogTabN * sizeof(LogEnt), kCols = 4u * 64u * B * sizeof(float);
+    switch (pl.kind) {
+    case Kind::March:
+    case Kind::Duo: {
+        // one f32 box slice of box_max voxels per wave (4 waves); a larger request
+        // caps the workgroups resident per CU (160 KiB of LDS per CU)
+        // (+ the log table and the record columns of the wide entropy march, k_march)
+        const size_t lds = cap_lds(P, pl.cap, B > 0 ? (size_t)P.box_max * 4u * sizeof(float) +
+                                                      (B >= 8 && method == 3 ? kTab + kCols : 0) : 0);
+        if (pl.kind == Kind::Duo) {
+            if constexpr (kNarrow) {
+                switch (pl.duo * 4 + method) {
+                case 9: VR_L((k_march_duo<B, 1, 2>), lds, vol, P); break;
+                case 10: VR_L((k_march_duo<B, 2, 2>), lds, vol, P); break;
+                case 13: VR_L((k_march_duo<B, 1, 3>), lds, vol, P); break;
+                case 14: VR_L((k_march_duo<B, 2, 3>), lds, vol, P); break;
+                case 17: VR_L((k_march_duo<B, 1, 4>), lds, vol, P); break;
+                case 18: VR_L((k_march_duo<B, 2, 4>), lds, vol, P); break;
+                default: return hipErrorInvalidValue;
                 }
-                const float *v = P.bvol ? P.bvol : vol;
-                switch (method * 2 + (P.bvol ? 1 : 0)) {
+                return hipGetLastError();
+            }
+            return hipErrorInvalidValue;
+        }
+        switch (method * 2 + (pl.count ? 1 : 0)) {
+        case 2: VR_L((k_march<B, 1, false>), lds, vol, P); break;
+        case 3: VR_L((k_march<B, 1, true>), lds, vol, P); break;
+        case 4: VR_L((k_march<B, 2, false>), lds, vol, P); break;
+        case 5: VR_L((k_march<B, 2, true>), lds, vol, P); break;
+        case 6: VR_L((k_march<B, 3, false>), lds, vol, P); break;
+        case 7: VR_L((k_march<B, 3, true>), lds, vol, P); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    case Kind::Quad:
+        if constexpr (B == 8) {
+            // entropy: the log table (qc_group) at the front
+            const size_t qlds = cap_lds(P, pl.cap, method == 3 ? kTab : 0);
+            // the micro-brick copy is passed as vol with its pitches
+            Params Q = P;
+            if (pl.brick) {
+                Q.sy = P.bsy;
+                Q.sz = P.bsz;
+            }
+            const float *v = pl.brick ? P.bvol : vol;
+            const int inst = method * 2 + (pl.brick ? 1 : 0);
+            if (pl.quad2) {  // two lanes per ray, two workgroups per tile
+                const dim3 grid2(((nslots + 7u) / 8u) * 16u);
+                switch (inst) {
                 case 2: hipLaunchKernelGGL((k_march_quad2<1, false>), grid2, block, qlds, s, v, Q); break;
                 case 3: hipLaunchKernelGGL((k_march_quad2<1, true>), grid2, block, qlds, s, v, Q); break;
                 case 4: hipLaunchKernelGGL((k_march_quad2<2, false>), grid2, block, qlds, s, v, Q); break;
                 case 5: hipLaunchKernelGGL((k_march_quad2<2, true>), grid2, block, qlds, s, v, Q); break;
                 case 6: hipLaunchKernelGGL((k_march_quad2<3, false>), grid2, block, qlds, s, v, Q); break;
                 case 7: hipLaunchKernelGGL((k_march_quad2<3, true>), grid2, block, qlds, s, v, Q); break;
+                default: return hipErrorInvalidValue;
                 }
                 return hipGetLastError();
             }
-            if (P.bvol) {
-                Params Q = P;
-                Q.sy = P.bsy;
-                Q.sz = P.bsz;
-                switch (method) {
-                case 1: hipLaunchKernelGGL((k_march_quad<1, true>), grid, block, qlds, s, P.bvol, Q); break;
-                case 2: hipLaunchKernelGGL((k_march_quad<2, true>), grid, block, qlds, s, P.bvol, Q); break;
-                case 3: hipLaunchKernelGGL((k_march_quad<3, true>), grid, block, qlds, s, P.bvol, Q); break;
-                }
-            } else {
-                switch (method) {
-                case 1: hipLaunchKernelGGL((k_march_quad<1, false>), grid, block, qlds, s, vol, P); break;
-                case 2: hipLaunchKernelGGL((k_march_quad<2, false>), grid, block, qlds, s, vol, P); break;
-                case 3: hipLaunchKernelGGL((k_march_quad<3, false>), grid, block, qlds, s, vol, P); break;
-                }
+            switch (inst) {
+            case 2: VR_L((k_march_quad<1, false>), qlds, v, Q); break;
+            case 3: VR_L((k_march_quad<1, true>), qlds, v, Q); break;
+            case 4: VR_L((k_march_quad<2, false>), qlds, v, Q); break;
+            case 5: VR_L((k_march_quad<2, true>), qlds, v, Q); break;
+            case 6: VR_L((k_march_quad<3, false>), qlds, v, Q); break;
+            case 7: VR_L((k_march_quad<3, true>), qlds, v, Q); break;
+            default: return hipErrorInvalidValue;
             }
             return hipGetLastError();
         }
-        if (P.path == 4 && method >= 1 && method <= 3) {
-            note_kernel("k_march_ws", B, method);
+        return hipErrorInvalidValue;
+    case Kind::Ws:
+        if constexpr (kNarrow) {
             switch (method) {
-            case 1: hipLaunchKernelGGL((k_march_ws<B, 1>), grid, block, 0, s, vol, P); break;
-            case 2: hipLaunchKernelGGL((k_march_ws<B, 2>), grid, block, 0, s, vol, P); break;
-            case 3: hipLaunchKernelGGL((k_march_ws<B, 3>), grid, block, kLogTabN * sizeof(LogEnt), s, vol, P); break;
+            case 1: VR_L((k_march_ws<B, 1>), 0, vol, P); break;
+            case 2: VR_L((k_march_ws<B, 2>), 0, vol, P); break;
+            case 3: VR_L((k_march_ws<B, 3>), kTab, vol, P); break;
+            default: return hipErrorInvalidValue;
             }
             return hipGetLastError();
         }
-        if (B < 8 && P.path == 0) P.path = 2;  // per-ray pipelined for narrow records
-        if constexpr (B == 1) {  // baked statistics (vr_stats.hip, bricked planes): paths 2, 7 only
-            if (method <= 0) P.path = 2;
-        }
-        if (P.path == 2 && P.avol && method >= 1 && method <= 3) {
-            // views along the volume's y / z on the axis-rows copy (vr_api.cpp
-            // ensure_axis_copy): the same march, gathers addressed with its strides
-            note_kernel(P.asy == 1 ? "k_march_pipe_yrows" : "k_march_pipe_zrows", B, method);
-            Params Q = P;
-            Q.sx = P.asx;
-            Q.sy = P.asy;
-            Q.sz = P.asz;
-            switch (method) {
-            case 1: hipLaunchKernelGGL((k_march_pipe<B, 1, 3>), grid, block, occupancy_lds(P), s, P.avol, Q); break;
-            case 2: hipLaunchKernelGGL((k_march_pipe<B, 2, 3>), grid, block, occupancy_lds(P), s, P.avol, Q); break;
+        return hipErrorInvalidValue;
+    case Kind::Pipe:
+        if constexpr (kNarrow) {
+            const size_t lds = cap_lds(P, pl.cap);
             // (the entropy march's LDS columns and table are part of the request)
-            case 3: hipLaunchKernelGGL((k_march_pipe<B, 3, 3>), grid, block, cap_lds(P, P.wg_per_cu, sizeof(EntropyLds<B>)), s, P.avol, Q); break;
+            const size_t lds3 = cap_lds(P, pl.cap, sizeof(EntropyLds<B>));
+            if (pl.axis) {
+                // views along the volume's y / z on the axis-rows copy (vr_api.cpp
+                // ensure_axis_copy): the same march, gathers addressed with its strides
+                Params Q = P;
+                Q.sx = P.asx;
+                Q.sy = P.asy;
+                Q.sz = P.asz;
+                switch (method) {
+                case 1: VR_L((k_march_pipe<B, 1, 3>), lds, P.avol, Q); break;
+                case 2: VR_L((k_march_pipe<B, 2, 3>), lds, P.avol, Q); break;
+                case 3: VR_L((k_march_pipe<B, 3, 3>), lds3, P.avol, Q); break;
+                default: return hipErrorInvalidValue;
+                }
+                return hipGetLastError();
             }
-            return hipGetLastError();
-        }
-        if (P.path == 2 && method >= -1 && method <= 3) {
-            note_kernel("k_march_pipe", B, method);
             switch (method) {
-            case 0:
+            case 0:  // baked statistics (vr_stats.hip, bricked planes), 32-bit offsets
                 if constexpr (B == 1) {
+                    switch (pl.plane_axis) {
                     // a baked plane's y- / z-rows copy (side and top views, gather8 MODE 4 / 5)
-                    if (P.plane_axis == 1) {
-                        note_kernel("k_march_pipe_plane_yrows", B, method);
-                        hipLaunchKernelGGL((k_march_pipe<1, 0, 4>), grid, block, occupancy_lds(P), s, vol, P);
-                    } else if (P.plane_axis == 2) {
-                        note_kernel("k_march_pipe_plane_zrows", B, method);
-                        hipLaunchKernelGGL((k_march_pipe<1, 0, 5>), grid, block, occupancy_lds(P), s, vol, P);
-                    } else if (P.plane_axis == 3) {  // 8 x 2 x 2 brick copy (MODE 6)
-                        note_kernel("k_march_pipe_plane8", B, method);
-                        hipLaunchKernelGGL((k_march_pipe<1, 0, 6>), grid, block, occupancy_lds(P), s, vol, P);
-                    } else {
-                        hipLaunchKernelGGL((k_march_pipe<1, 0>), grid, block, occupancy_lds(P), s, vol, P);
+                    case 1: VR_L((k_march_pipe<1, 0, 4>), lds, vol, P); break;
+                    case 2: VR_L((k_march_pipe<1, 0, 5>), lds, vol, P); break;
+                    case 3: VR_L((k_march_pipe<1, 0, 6>), lds, vol, P); break;  // 8 x 2 x 2 brick copy (MODE 6)
+                    default: VR_L((k_march_pipe<1, 0>), lds, vol, P); break;
                     }
                     break;
                 }
                 return hipErrorInvalidValue;
-            case -1:
+            case -1:  // baked, 64-bit offsets
                 if constexpr (B == 1) {
-                    hipLaunchKernelGGL((k_march_pipe<1, -1>), grid, block, occupancy_lds(P), s, vol, P);
+                    VR_L((k_march_pipe<1, -1>), lds, vol, P);
                     break;
                 }
                 return hipErrorInvalidValue;
-            case 1: hipLaunchKernelGGL((k_march_pipe<B, 1>), grid, block, occupancy_lds(P), s, vol, P); break;
-            case 2: hipLaunchKernelGGL((k_march_pipe<B, 2>), grid, block, occupancy_lds(P), s, vol, P); break;
-            case 3: hipLaunchKernelGGL((k_march_pipe<B, 3>), grid, block, cap_lds(P, P.wg_per_cu, sizeof(EntropyLds<B>)), s, vol, P); break;
+            case 1: VR_L((k_march_pipe<B, 1>), lds, vol, P); break;
+            case 2: VR_L((k_march_pipe<B, 2>), lds, vol, P); break;
+            case 3: VR_L((k_march_pipe<B, 3>), lds3, vol, P); break;
+            default: return hipErrorInvalidValue;
             }
             return hipGetLastError();
         }
-    }
-    if constexpr (!COUNT && (B == 16 || B == 32)) {
-        // wide records, mean / variance: the quad-cooperative march (k_march_wq),
-        // except row-aligned views of 16-bin records, whose lane-owned 64-B records
-        // already sit side by side (k_march_wide; 1024^3 x 16 C0 2.79 vs 3.90 ms;
-        // profiles/r02/wide_records.log).  VR_WIDE=1 / 2 forces one; VR_PATH=1 and
-        // coarse row-aligned full frames keep the LDS box (vr_api.cpp).  Entropy
-        // stays on k_march: unrolled over a batch its per-bin logarithms need more
-        // than 256 VGPRs (B = 16: 512 + spills).
-        if (P.path != 1 && (method == 1 || method == 2 || (method == 3 && WQ3))) {
+        return hipErrorInvalidValue;
+    case Kind::Wide:
+    case Kind::Wq:
+        if constexpr (B == 16 || B == 32) {
             // an occupancy cap's LDS request leaves room for the kernel's static LDS
             // (the entropy march's log table and record columns)
-            const size_t wl = cap_lds(P, P.wg_per_cu, 0,
-                                      method == 3 ? kLogTabN * sizeof(LogEnt) + (B >= 32 ? 4 * 64 * B * sizeof(float) : 4) : 64);
-            int kind = (B == 16 && !P.oblique && method != 3) ? 1 : 2;
-            if (const char *ew = tuning("VR_WIDE")) {
-                const int v = std::atoi(ew);
-                if (v == 1 || v == 2) kind = v;
-            }
-            if (method == 3) kind = 2;  // k_march_wide: mean and variance only
-            // k_march_wq pixels: 16x4 blocks per wave (a quad = a pixel column) beat a
-            // 64-pixel row per wave: 1024^3 x 32 C1 12.44 -> 11.77 ms, C0 6.64 -> 6.56,
-            // 1024^3 x 16 C1 6.78 -> 6.65 (profiles/r02/wide_records.log); VR_WQ_MAP=0: rows
-            P.wq_map = 1;
-            if (const char *em = tuning("VR_WQ_MAP")) P.wq_map = std::atoi(em) != 0;
-            if (kind == 1) {
-                note_kernel("k_march_wide", B, method);
-                // a 16x4 pixel block per wave (1024^3 x 16 1080p C0 m1 2.719 -> 2.673
-                // ms, profiles/r06/segmap/wide_1024x16.log); VR_WIDE_MAP=0: rows
-                P.seg_map = 1;
-                if (const char *em = tuning("VR_WIDE_MAP")) P.seg_map = std::atoi(em) != 0;
-                if (method == 1)
-                    hipLaunchKernelGGL((k_march_wide<B, 1>), grid, block, wl, s, vol, P);
-                else
-                    hipLaunchKernelGGL((k_march_wide<B, 2>), grid, block, wl, s, vol, P);
-            } else {
-                note_kernel("k_march_wq", B, method);
-                if (method == 1)
-                    hipLaunchKernelGGL((k_march_wq<B, 1>), grid, block, wl, s, vol, P);
-                else if (method == 2)
-                    hipLaunchKernelGGL((k_march_wq<B, 2>), grid, block, wl, s, vol, P);
-                else if constexpr (WQ3)
-                    hipLaunchKernelGGL((k_march_wq<B, 3>), grid, block, wl, s, vol, P);
+            const size_t wl = cap_lds(P, pl.cap, 0, method == 3 ? kTab + (B >= 32 ? kCols : 4) : 64);
+            switch ((pl.kind == Kind::Wide ? 0 : 4) + method) {
+            case 1: VR_L((k_march_wide<B, 1>), wl, vol, P); break;
+            case 2: VR_L((k_march_wide<B, 2>), wl, vol, P); break;
+            case 5: VR_L((k_march_wq<B, 1>), wl, vol, P); break;
+            case 6: VR_L((k_march_wq<B, 2>), wl, vol, P); break;
+            case 7:
+                if constexpr (WQ3) {
+                    VR_L((k_march_wq<B, 3>), wl, vol, P);
+                    break;
+                }
+                return hipErrorInvalidValue;
+            default: return hipErrorInvalidValue;
             }
             return hipGetLastError();
         }
-    }
-    if (!COUNT) note_kernel("k_march", B, method);
-    if (method >= 1 && method <= 3) {
-        // the LDS-box march: a wave takes a 16x4-pixel block, whose footprint box is
-        // compact (512^3 x 8 C0 1080p: ~70 voxels per wave-step instead of
-        // ~140-210 for a 64-pixel row): m1 0.869 -> 0.723 ms, m2 0.760 -> 0.627
-        // (profiles/r03/box_map.log); VR_BOX_MAP=0 keeps the rows
-        P.wq_map = 1;
-        if (const char *em = tuning("VR_BOX_MAP")) P.wq_map = std::atoi(em) != 0;
-    }
-    if constexpr (!COUNT && B > 0 && B <= 8) {
-        // P.duo samples per footprint box (k_march_duo; fill_params: coarse
-        // row-aligned 8-bin full frames, VR_DUO)
-        const int k = P.duo;
-        if (k >= 2 && k <= 4 && (method == 1 || method == 2) && P.box_max > 0) {
-            note_kernel(k == 2 ? "k_march_duo" : k == 3 ? "k_march_duo3" : "k_march_duo4", B, method);
-#define VR_DUO_L(MM, KK) hipLaunchKernelGGL((k_march_duo<B, MM, KK>), grid, block, lds, s, vol, P)
-            switch (k * 4 + method) {
-            case 9: VR_DUO_L(1, 2); break;
-            case 10: VR_DUO_L(2, 2); break;
-            case 13: VR_DUO_L(1, 3); break;
-            case 14: VR_DUO_L(2, 3); break;
-            case 17: VR_DUO_L(1, 4); break;
-            case 18: VR_DUO_L(2, 4); break;
-            }
-#undef VR_DUO_L
-            return hipGetLastError();
-        }
-    }
-    switch (method) {
-    case 0:
-    case -1:  // baked statistics: the pipelined / segmented marches only (bricked planes)
         return hipErrorInvalidValue;
-    case 1: hipLaunchKernelGGL((k_march<B, 1, COUNT>), grid, block, lds, s, vol, P); break;
-    case 2: hipLaunchKernelGGL((k_march<B, 2, COUNT>), grid, block, lds, s, vol, P); break;
-    case 3: hipLaunchKernelGGL((k_march<B, 3, COUNT>), grid, block, lds, s, vol, P); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
-template <bool COUNT>
-static hipError_t march_dispatch(int nb, int method, const float *vol, const Params &P,
-                                 uint32_t nslots, hipStream_t s) {
-    switch (nb) {
-    case 1: return march_b<1, COUNT>(method, vol, P, nslots, s);
-    case 2: return march_b<2, COUNT>(method, vol, P, nslots, s);
-    case 4: return march_b<4, COUNT>(method, vol, P, nslots, s);
-    case 8: return march_b<8, COUNT>(method, vol, P, nslots, s);
-    case 16: return march_b<16, COUNT>(method, vol, P, nslots, s);
-    case 32: return march_b<32, COUNT>(method, vol, P, nslots, s);
-    default: return march_b<0, COUNT>(method, vol, P, nslots, s);
-    }
-}
+#undef VR_L
 
-hipError_t launch_march(int nb, int method, const float *vol, const Params &P,
-                        uint32_t nslots, bool count, hipStream_t s) {
+hipError_t launch_plan(const MarchPlan &pl, const void *vol, const Params &P, uint32_t nslots,
+                       hipStream_t s) {
     if (nslots == 0) return hipSuccess;
-    if (method == 7 || method == -7)  // corner-mean state along the ray: vr_m7.hip
-        return count ? hipErrorInvalidValue : launch_march_m7(nb, method, vol, P, nslots, s);
-    return count ? march_dispatch<true>(nb, method, vol, P, nslots, s)
-                 : march_dispatch<false>(nb, method, vol, P, nslots, s);
+    if (!pl.count) plan_kernel_name(pl, g_last_kernel, sizeof g_last_kernel);
+    const float *v = static_cast<const float *>(vol);
+    switch (pl.kind) {
+    case Kind::None: return hipErrorInvalidValue;
+    case Kind::PipeH: return launch_march_h(pl, vol, P, nslots, s);
+    case Kind::M7:
+    case Kind::M7Pipe:
+    case Kind::M7Quad:
+    case Kind::M7Wq: return launch_march_m7(pl, v, P, nslots, s);
+    case Kind::Seg:
+    case Kind::SegHead: return launch_march_seg(pl, v, P, nslots, s);
+    default: break;
+    }
+    switch (pl.B) {
+    case 1: return launch_b<1>(pl, v, P, nslots, s);
+    case 2: return launch_b<2>(pl, v, P, nslots, s);
+    case 4: return launch_b<4>(pl, v, P, nslots, s);
+    case 8: return launch_b<8>(pl, v, P, nslots, s);
+    case 16: return launch_b<16>(pl, v, P, nslots, s);
+    case 32: return launch_b<32>(pl, v, P, nslots, s);
+    default: return launch_b<0>(pl, v, P, nslots, s);
+    }
 }
 
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s) {

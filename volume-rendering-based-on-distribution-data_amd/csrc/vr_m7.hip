@@ -602,103 +602,65 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_WIDE_MIN
 }
 
 // ------------------------------ launcher ----------------------------------
+// Switches on the plan (vr_plan.cpp plan_m7 chose the kind, the pixel maps and
+// the occupancy cap).
 
 template <int B>
-static hipError_t march_m7_b(int method, const float *vol, const Params &P, uint32_t nslots,
-                             hipStream_t s) {
+static hipError_t march_m7_b(const MarchPlan &pl, const float *vol, const Params &P,
+                             uint32_t nslots, hipStream_t s) {
     const dim3 grid(nslots), block(256);
-    if (method == -7) {  // method 7 over the baked corner means (plane 3, vr_stats.hip)
-        if constexpr (B == 1) {
-            // 4-byte corners: the plain march (the look-ahead gather of
-            // k_march_m7_pipe only adds loads), 4 workgroups per CU on row-aligned
-            // views, 2 on oblique ones (1024^3 C0 0.68 -> 0.64 ms, C1 2.03 -> 1.67;
-            // profiles/r02/baked_m7.log)
-            note_kernel("k_march_m7", B, method);
-            hipLaunchKernelGGL((k_march_m7<1, true>), grid, block,
-                               cap_lds(P, P.wg_per_cu > 0 ? P.wg_per_cu : (P.oblique ? 2 : 4)), s,
-                               vol, P);
-            return hipGetLastError();
+    const size_t lds = cap_lds(P, pl.cap);
+    switch (pl.kind) {
+    case Kind::M7:
+        if (pl.method == -7) {  // over the baked corner means (plane 3, vr_stats.hip)
+            if constexpr (B == 1) {
+                hipLaunchKernelGGL((k_march_m7<1, true>), grid, block, lds, s, vol, P);
+                return hipGetLastError();
+            }
+            return hipErrorInvalidValue;
         }
-        return hipErrorInvalidValue;
-    }
-    if (method != 7) return hipErrorInvalidValue;
-    if constexpr (B == 8) {
-        // oblique views with the method-7 grid equal to the volume: the
-        // quad-cooperative march (VR_M7_QUAD=0 disables), 2 workgroups per CU
-        const char *eq = tuning("VR_M7_QUAD");
-        const bool quad = !(eq && std::atoi(eq) == 0);
-        if (quad && P.oblique && P.m7x == P.nx && P.m7y == P.ny && P.m7z == P.nz) {
-            const size_t qlds = cap_lds(P, P.wg_per_cu > 0 ? P.wg_per_cu : 2);
-            if (P.bvol) {
-                note_kernel("k_march_m7_quad_brick", B, method);
+        hipLaunchKernelGGL((k_march_m7<B>), grid, block, lds, s, vol, P);
+        return hipGetLastError();
+    case Kind::M7Quad:
+        if constexpr (B == 8) {
+            if (pl.brick) {  // the micro-brick copy, passed as vol with its pitches
                 Params Q = P;
                 Q.sy = P.bsy;
                 Q.sz = P.bsz;
-                hipLaunchKernelGGL(k_march_m7_quad<true>, grid, block, qlds, s, P.bvol, Q);
+                hipLaunchKernelGGL(k_march_m7_quad<true>, grid, block, lds, s, P.bvol, Q);
             } else {
-                note_kernel("k_march_m7_quad", B, method);
-                hipLaunchKernelGGL(k_march_m7_quad<false>, grid, block, qlds, s, vol, P);
+                hipLaunchKernelGGL(k_march_m7_quad<false>, grid, block, lds, s, vol, P);
             }
             return hipGetLastError();
         }
-    }
-    if constexpr (B == 16 || B == 32) {
-        // wide records: quad-cooperative refreshes (VR_M7_WQ=0: k_march_m7)
-        const char *eq = tuning("VR_M7_WQ");
-        if (!(eq && std::atoi(eq) == 0)) {
-            note_kernel("k_march_m7wq", B, method);
-            Params Q = P;
-            Q.wq_map = M7_WQ_MAP;
-            if (const char *em = tuning("VR_WQ_MAP")) Q.wq_map = std::atoi(em) != 0;
-            hipLaunchKernelGGL((k_march_m7wq<B>), grid, block, occupancy_lds(P), s, vol, Q);
+        return hipErrorInvalidValue;
+    case Kind::M7Wq:
+        if constexpr (B == 16 || B == 32) {
+            hipLaunchKernelGGL((k_march_m7wq<B>), grid, block, lds, s, vol, P);
             return hipGetLastError();
         }
-    }
-    if constexpr (B > 0 && B <= 8) {
-        // pipelined corner gathers (VR_M7_PIPE=0: the plain march); oblique views
-        // at 2 workgroups per CU (1024^3x8 C1: 8.53 -> 7.45 ms; C0 is fastest
-        // uncapped, 1.53 ms; profiles/r02/m7_pipe.log)
-        const char *ep = tuning("VR_M7_PIPE");
-        if (!(ep && std::atoi(ep) == 0)) {
-            note_kernel("k_march_m7_pipe", B, method);
-            hipLaunchKernelGGL((k_march_m7_pipe<B>), grid, block,
-                               cap_lds(P, P.wg_per_cu > 0 ? P.wg_per_cu
-                                                          : (P.oblique && B == 8 ? 2 : 0)),
-                               s, vol, P);
+        return hipErrorInvalidValue;
+    case Kind::M7Pipe:
+        if constexpr (B > 0 && B <= 8) {
+            hipLaunchKernelGGL((k_march_m7_pipe<B>), grid, block, lds, s, vol, P);
             return hipGetLastError();
         }
+        return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
     }
-    // oblique views at 3 workgroups per CU when B = 8 (the measured case): fewer
-    // corner-mean refreshes in flight, fewer L2 re-reads (1024^3x8 C1 9.94 ->
-    // 8.29 ms; row-aligned C0 is fastest uncapped)
-    note_kernel("k_march_m7", B, method);
-    hipLaunchKernelGGL((k_march_m7<B>), grid, block,
-                       cap_lds(P, P.wg_per_cu > 0 ? P.wg_per_cu : (P.oblique && B == 8 ? 3 : 0)),
-                       s, vol, P);
-    return hipGetLastError();
 }
 
-hipError_t launch_march_m7(int nb, int method, const float *vol, const Params &P0,
-                           uint32_t nslots, hipStream_t s) {
-    if (nslots == 0) return hipSuccess;
-    // the one-lane method-7 marches (k_march_m7_pipe / k_march_m7): a 16x4 pixel
-    // block per wave, except 8+-bin row-aligned views of a fine volume (< 4 pixels
-    // per voxel of the x-y face), which keep 64-pixel rows: 256^3 x 4 at 512^2 C0
-    // 0.322 -> 0.222 ms, C1 0.201 -> 0.175; 512^3 x 8 1080p C0 1.201 -> 1.125;
-    // 1024^3 x 4 C0 0.795 -> 0.775, C1 2.67 -> 2.39; 1024^3 x 8 C0 1.447 vs 1.468
-    // (rows; profiles/r06/segmap/m7_*.log).  VR_M7_MAP=0/1 overrides.
-    Params P = P0;
-    P.seg_map = !(nb >= 8 && !P.oblique &&
-                  (uint64_t)P.CW * P.CH < 4ull * (uint64_t)P.nx * (uint64_t)P.ny);
-    if (const char *e = tuning("VR_M7_MAP")) P.seg_map = std::atoi(e) != 0;
-    switch (nb) {
-    case 1: return march_m7_b<1>(method, vol, P, nslots, s);
-    case 2: return march_m7_b<2>(method, vol, P, nslots, s);
-    case 4: return march_m7_b<4>(method, vol, P, nslots, s);
-    case 8: return march_m7_b<8>(method, vol, P, nslots, s);
-    case 16: return march_m7_b<16>(method, vol, P, nslots, s);
-    case 32: return march_m7_b<32>(method, vol, P, nslots, s);
-    default: return march_m7_b<0>(method, vol, P, nslots, s);
+hipError_t launch_march_m7(const MarchPlan &pl, const float *vol, const Params &P, uint32_t nslots,
+                           hipStream_t s) {
+    if (pl.method != 7 && pl.method != -7) return hipErrorInvalidValue;
+    switch (pl.B) {
+    case 1: return march_m7_b<1>(pl, vol, P, nslots, s);
+    case 2: return march_m7_b<2>(pl, vol, P, nslots, s);
+    case 4: return march_m7_b<4>(pl, vol, P, nslots, s);
+    case 8: return march_m7_b<8>(pl, vol, P, nslots, s);
+    case 16: return march_m7_b<16>(pl, vol, P, nslots, s);
+    case 32: return march_m7_b<32>(pl, vol, P, nslots, s);
+    default: return march_m7_b<0>(pl, vol, P, nslots, s);
     }
 }
 

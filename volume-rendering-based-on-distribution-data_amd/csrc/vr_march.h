@@ -77,7 +77,7 @@ __device__ __forceinline__ void tile_pixel(uint32_t t, uint32_t &lx, uint32_t &l
 }
 // P.seg_map: a wave's 64 lanes take a 16x4 pixel block of the tile instead of a
 // 64-pixel row (compact footprints per load instruction; where it is the default:
-// vr_api.cpp fill_params)
+// vr_plan.cpp)
 __device__ __forceinline__ void lane_pixel(const Params &P, uint32_t t, uint32_t &lx, uint32_t &ly) {
     if (P.seg_map) {
         lx = (t >> 6) * 16u + (t & 15u);

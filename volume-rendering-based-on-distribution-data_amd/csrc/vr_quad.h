@@ -116,9 +116,6 @@ __device__ __forceinline__ float qc_blend(const FootPacked &fp, float s0, float 
 #define VR_WIDE_MINW 1      // waves per SIMD the register allocation must allow
 #endif
 constexpr bool WQ3 = true;  // entropy through the quad-cooperative wide march
-#ifndef M7_WQ_MAP
-#define M7_WQ_MAP 1         // k_march_m7wq pixel map default (P.wq_map)
-#endif
 #ifndef VR_QUAD_WAVES
 #define VR_QUAD_WAVES 1  // minimum waves per SIMD the register allocation must allow
 #endif

@@ -373,66 +373,52 @@ static hipError_t seg_axis_launch(int method, const Params &P, uint32_t nslots, 
     return hipGetLastError();
 }
 
+// |seg_lanes| lanes per ray, plain (S > 0) or pipelined (S < 0) windows; over an
+// axis-rows copy (pl.axis) pipelined windows only
 template <int B>
-static bool seg_b(int method, int S, const float *vol, const Params &P, uint32_t nslots,
-                  hipStream_t s, hipError_t &err) {
-    if (P.avol && method >= 1 && method <= 3) {  // axis views: pipelined windows only
-        switch (S) {
-        case -2: err = seg_axis_launch<B, 2>(method, P, nslots, s); return true;
-        case -4: err = seg_axis_launch<B, 4>(method, P, nslots, s); return true;
-        default: return false;
+static hipError_t seg_b(const MarchPlan &pl, const float *vol, const Params &P, uint32_t nslots,
+                        hipStream_t s) {
+    const int method = pl.method;
+    if (pl.axis) {
+        switch (pl.seg_lanes) {
+        case -2: return seg_axis_launch<B, 2>(method, P, nslots, s);
+        case -4: return seg_axis_launch<B, 4>(method, P, nslots, s);
+        default: return hipErrorInvalidValue;
         }
     }
-    // S > 0: plain windows; S < 0: pipelined windows of |S| lanes (the
-    // dispatch uses 4, -2 and -4; 2 is kept as the plain counterpart of -2)
-    switch (S) {
-    case 2: err = seg_launch<B, 2, false>(method, vol, P, nslots, s); return true;
-    case 4: err = seg_launch<B, 4, false>(method, vol, P, nslots, s); return true;
-    case -2: err = seg_launch<B, 2, true>(method, vol, P, nslots, s); return true;
-    case -4: err = seg_launch<B, 4, true>(method, vol, P, nslots, s); return true;
-    default: return false;
+    switch (pl.seg_lanes) {
+    case 2: return seg_launch<B, 2, false>(method, vol, P, nslots, s);
+    case 4: return seg_launch<B, 4, false>(method, vol, P, nslots, s);
+    case -2: return seg_launch<B, 2, true>(method, vol, P, nslots, s);
+    case -4: return seg_launch<B, 4, true>(method, vol, P, nslots, s);
+    default: return hipErrorInvalidValue;
     }
 }
 
-bool launch_march_seg(int nb, int method, int S, const float *vol, const Params &P,
-                      uint32_t nslots, hipStream_t s, hipError_t &err) {
-    if (method < (nb == 1 ? -1 : 1) || method > 3) return false;
-    bool ok = false;
-    if (nb == 8 && S == -2 && (method == 1 || method == 2) && P.head_slots > 0 &&
-        P.head_slots < nslots && (P.head_slots & 7u) == 0 &&
-        (P.head_lanes == -2 || P.head_lanes == -4 || P.head_lanes == -8)) {
-        if (P.head_tail == 1)
-            err = P.head_lanes == -2 ? pipe_head_launch<8, 2>(method, vol, P, nslots, s)
-                : P.head_lanes == -4 ? pipe_head_launch<8, 4>(method, vol, P, nslots, s)
-                                     : pipe_head_launch<8, 8>(method, vol, P, nslots, s);
-        else
-            err = P.head_lanes == -2 ? seg_head_launch<8, 2>(method, vol, P, nslots, s)
-                : P.head_lanes == -4 ? seg_head_launch<8, 4>(method, vol, P, nslots, s)
-                                     : seg_head_launch<8, 8>(method, vol, P, nslots, s);
-        char kind[48];
-        snprintf(kind, sizeof kind, "k_march_segp%d_head_%s%s", -P.head_lanes,
-                 P.head_tail == 1 ? "pipe" : "segp2",
-                 P.avol ? (P.asy == 1 ? "_yrows" : "_zrows") : "");
-        note_kernel(kind, nb, method);
-        return true;
+// Kind::Seg and Kind::SegHead of the plan (vr_plan.cpp plan_seg)
+hipError_t launch_march_seg(const MarchPlan &pl, const float *vol, const Params &P,
+                            uint32_t nslots, hipStream_t s) {
+    const int method = pl.method;
+    if (pl.kind == Kind::SegHead) {
+        if (pl.B != 8 || P.head_slots == 0 || P.head_slots >= nslots) return hipErrorInvalidValue;
+        const bool pipe = pl.head_tail == 1;
+        switch (pl.head_lanes) {
+        case -2: return pipe ? pipe_head_launch<8, 2>(method, vol, P, nslots, s)
+                             : seg_head_launch<8, 2>(method, vol, P, nslots, s);
+        case -4: return pipe ? pipe_head_launch<8, 4>(method, vol, P, nslots, s)
+                             : seg_head_launch<8, 4>(method, vol, P, nslots, s);
+        case -8: return pipe ? pipe_head_launch<8, 8>(method, vol, P, nslots, s)
+                             : seg_head_launch<8, 8>(method, vol, P, nslots, s);
+        default: return hipErrorInvalidValue;
+        }
     }
-    switch (nb) {
-    case 1: ok = seg_b<1>(method, S, vol, P, nslots, s, err); break;
-    case 2: ok = seg_b<2>(method, S, vol, P, nslots, s, err); break;
-    case 4: ok = seg_b<4>(method, S, vol, P, nslots, s, err); break;
-    case 8: ok = seg_b<8>(method, S, vol, P, nslots, s, err); break;
-    default: return false;
+    switch (pl.B) {
+    case 1: return seg_b<1>(pl, vol, P, nslots, s);
+    case 2: return seg_b<2>(pl, vol, P, nslots, s);
+    case 4: return seg_b<4>(pl, vol, P, nslots, s);
+    case 8: return seg_b<8>(pl, vol, P, nslots, s);
+    default: return hipErrorInvalidValue;
     }
-    if (ok) {
-        char kind[40];
-        snprintf(kind, sizeof kind, S < 0 ? "k_march_segp%d%s" : "k_march_seg%d%s", S < 0 ? -S : S,
-                 (P.avol && method >= 1 && method <= 3) ? (P.asy == 1 ? "_yrows" : "_zrows")
-                 : (nb == 1 && method == 0 && P.plane_axis)
-                     ? (P.plane_axis == 1 ? "_plane_yrows" : P.plane_axis == 2 ? "_plane_zrows" : "_plane8")
-                 : "");
-        note_kernel(kind, nb, method);
-    }
-    return ok;
 }
 
 }  // namespace vr
