@@ -11,7 +11,8 @@
  *
  * Part 2 -- extensions (vr_*): explicit-parameter render with tile lists for
  * the multi-GPU image split, on-device synthetic volumes, the footprint counter
- * used for the roofline, and error reporting.  The library never calls exit():
+ * used for the roofline, GMM volumes (fp32 / f16 records, z-slab chains, baked
+ * mean / variance planes), and error reporting.  The library never calls exit():
  * failures are recorded for vr_last_error() (the reference's checkCudaErrors
  * printed and exited, C:201-216).
  *
@@ -541,6 +542,61 @@ int64_t vr_gmm_count_footprint(const vr_render_desc *desc);
  * The counting launch also writes the slab's alive list out (as a render
  * would) but no pixels.  Synchronous. */
 int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_slab *slab);
+
+/* Baked GMM statistics.  The mean and the 16 x variance
+ * vr_render_gmm decodes from the 8 corner mixtures of every sample are pure
+ * functions of one voxel, so they can be decoded once per voxel into two float
+ * planes -- plane 0 the mean (queryMethod 1), plane 1 16 x the variance
+ * (queryMethod 2), each the bits the march's decode produces -- and a frame
+ * rendered from the planes with the plane march of vr_render: bit-identical to
+ * vr_render_gmm, 4 bytes per corner voxel read instead of 8K / 12K (f16: 4K / 6K).
+ * The planes are whole-volume (X x Y x Z) in the layout of vr_bake_stats:
+ * 16 x 2 x 1 bricks, sy = ((X - 1) / 15 + 1) * 32, sz = ((Y + 1) / 2) * sy,
+ * voxel (x, y, z) at z * sz + (y / 2) * sy + (y % 2) * 16 + (x / 15) * 32 + x % 15
+ * (and, for x = 15 k > 0, also at offset 15 of brick k - 1), sz * Z floats each,
+ * plane 1 directly after plane 0.
+ *
+ * vr_bake_gmm_stats: bakes the selected slot's resident slices
+ * [z_base, z_base + nslices), fp32 or f16, into the planes.  The first call
+ * allocates both planes for the volume's dims (zeroed); later calls must come
+ * from a volume of the same dims (VR_ERR_STATE otherwise).  One pass over the
+ * records fills both planes.  The kernel is queued on the library stream like
+ * vr_render_gmm, so an adopted buffer must stay unchanged until that stream has
+ * passed it; which slices are baked is recorded at once.  Baking a slice again
+ * is allowed and rewrites the same values.  VR_ERR_STATE: no GMM volume in the
+ * selected slot.  VR_ERR_HIP: the planes could not be allocated; nothing has
+ * changed.  VR_ERR_UNSUPPORTED: more than 65535 voxels along x or y, or more
+ * than 65535 resident slices.
+ * The planes belong to no slot and to no resident records: they survive
+ * vr_init_gmm*, vr_synthesize_gmm*, vr_convert_gmm_f16, vr_free_gmm and
+ * vr_gmm_select, so a volume that never fits in HBM is baked slab by slab
+ * (make a slab resident, bake, free, next slab; any order, overlaps allowed)
+ * and then rendered with no records resident.  The library cannot see that
+ * records changed: A CALLER WHO CHANGES THE VOLUME'S RECORDS (new data of the
+ * same dims, or records modified in place) MUST CALL vr_release_gmm_stats
+ * BEFORE BAKING AGAIN, or frames mix old and new slices.
+ *
+ * vr_release_gmm_stats: frees the planes (freeCudaBuffers does too).
+ *
+ * vr_gmm_stats_info: the planes' dims, the device pointer of plane 0 (NULL: no
+ * planes), a plane's length in floats and the number of distinct slices baked;
+ * any argument may be NULL.
+ *
+ * vr_render_gmm_baked: a whole frame of queryMethod 1 or 2 (others:
+ * VR_ERR_UNSUPPORTED) from the planes; VR_ERR_STATE unless all Z slices are
+ * baked.  No GMM records need be resident, and vr_render_gmm is unaffected by
+ * the planes: it keeps decoding the records per step.  desc: everything
+ * vr_render takes -- d_output_f, d_steps and d_tile_list / n_tiles (padding
+ * entries, misses written as 0), which gives GMM volumes the image-tile
+ * multi-GPU split vr_render_gmm refuses.  The march reads the x-row bricks for
+ * every view (no layout copies of GMM planes); vr_last_kernel names the plane
+ * march, "<B=1,M=0>" (M=-1: planes beyond 32-bit indices).  Asynchronous on
+ * the library stream. */
+int vr_bake_gmm_stats(void);
+int vr_release_gmm_stats(void);
+int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_floats,
+                      int *slices_baked);
+int vr_render_gmm_baked(const vr_render_desc *desc);
 
 /* library version string */
 const char *vr_version(void);

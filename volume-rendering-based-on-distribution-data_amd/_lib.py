@@ -103,6 +103,7 @@ EXPORTS = [
     "vr_set_tuning", "vr_clear_tuning", "vr_stream_read", "vr_set_layout_budget",
     "vr_layout_info", "vr_init_distribution_f16", "vr_convert_f16", "vr_volume_dtype",
     "vr_init_gmm_f16", "vr_synthesize_gmm_f16", "vr_convert_gmm_f16", "vr_gmm_dtype",
+    "vr_bake_gmm_stats", "vr_release_gmm_stats", "vr_gmm_stats_info", "vr_render_gmm_baked",
 ]
 
 _lib = None
@@ -233,6 +234,14 @@ def load() -> ctypes.CDLL:
     L.vr_gmm_select.restype = ctypes.c_int
     L.vr_gmm_count_footprint_slab.argtypes = [ctypes.POINTER(RenderDesc), ctypes.POINTER(GmmSlab)]
     L.vr_gmm_count_footprint_slab.restype = ctypes.c_int64
+    L.vr_bake_gmm_stats.argtypes = []
+    L.vr_bake_gmm_stats.restype = i32
+    L.vr_release_gmm_stats.argtypes = []
+    L.vr_release_gmm_stats.restype = i32
+    L.vr_gmm_stats_info.argtypes = [vp] * 4
+    L.vr_gmm_stats_info.restype = i32
+    L.vr_render_gmm_baked.argtypes = [ctypes.POINTER(RenderDesc)]
+    L.vr_render_gmm_baked.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

@@ -582,6 +582,41 @@ def gmm_count_footprint(desc: RenderDesc, slab: Optional[_lib.GmmSlab] = None) -
     return int(check(L.vr_gmm_count_footprint_slab(ctypes.byref(desc), ctypes.byref(slab))))
 
 
+# ------------------------------------- baked GMM statistics
+
+def bake_gmm_stats() -> None:
+    """Decode the selected slot's resident slices once per voxel into the library's
+    two whole-volume GMM planes (mean, 16 x variance; include/vr.h
+    vr_bake_gmm_stats), queued on the library stream.  The first call allocates
+    the planes; they belong to no slot and outlive the records, so a volume is
+    baked slab by slab (init_gmm / bake_gmm_stats / free_gmm per slab).  Records
+    that change need release_gmm_stats() before they are baked again."""
+    check(_lib.load().vr_bake_gmm_stats())
+
+
+def release_gmm_stats() -> None:
+    """Free the baked GMM planes."""
+    check(_lib.load().vr_release_gmm_stats())
+
+
+def gmm_stats_info():
+    """((X, Y, Z), planes_ptr, plane_floats, slices_baked) of the baked GMM planes;
+    planes_ptr None = no planes.  Plane 1 (16 x variance) follows plane 0 (mean)
+    at planes_ptr + 4 * plane_floats bytes."""
+    e = Extent()
+    p, n, k = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_int()
+    check(_lib.load().vr_gmm_stats_info(ctypes.byref(e), ctypes.byref(p), ctypes.byref(n),
+                                        ctypes.byref(k)))
+    return (e.width, e.height, e.depth), p.value, n.value, k.value
+
+
+def render_gmm_baked(desc: RenderDesc) -> None:
+    """A whole frame of query method 1 / 2 from the baked GMM planes (asynchronous):
+    bit-identical to render_gmm, with the plane march of render().  Takes tile
+    lists, d_output_f and d_steps like render(); every slice must be baked."""
+    check(_lib.load().vr_render_gmm_baked(ctypes.byref(desc)))
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -596,5 +631,6 @@ __all__ = [
     "init_gmm", "synthesize_gmm", "gmm_info", "free_gmm", "gmm_select", "gmm_slab", "render_gmm",
     "gmm_count_footprint", "bake_stats", "release_stats", "stats_info", "set_layout_budget",
     "layout_info", "convert_f16", "volume_dtype", "convert_gmm_f16", "gmm_dtype",
+    "bake_gmm_stats", "release_gmm_stats", "gmm_stats_info", "render_gmm_baked",
     "VRError", "PAD",
 ]

@@ -72,6 +72,17 @@ struct State {
     // chain holds a front and a back z-range)
     Gmm gmm_parked[2];
     int gmm_slot = 0;
+    // baked GMM statistics (vr_bake_gmm_stats, vr_gmm.hip k_bake_gmm): two
+    // whole-volume planes of `plane` floats, the mean and 16 x variance of every
+    // voxel of an nx x ny x nz volume, filled slab by slab (slice[z]: baked);
+    // tied to no slot and to no resident records
+    struct GmmStats {
+        float *buf = nullptr;
+        int nx = 0, ny = 0, nz = 0;
+        uint64_t plane = 0, sy = 0, sz = 0;  // plane_pitches
+        std::vector<unsigned char> slice;
+        int nbaked = 0;
+    } gstats;
     // baked statistics (basicDataProcessing / vr_bake_stats, vr_stats.hip):
     // four planes of stats_plane floats for the raw volume (methods 1/2/3 and
     // method 7's corner mean) and
@@ -519,16 +530,20 @@ void device_lds(int &per_cu, int &per_wg) {
     per_wg = wg;
 }
 
-int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
-                bool for_render = false) {
-    if (!d) return fail(VR_ERR_ARG, "null render descriptor");
+// the voxel grid a frame's Params describe: dims, bins per record and the
+// record pitches of a row / slice
+struct FrameVol {
+    int nx, ny, nz, nb;
+    uint64_t sy, sz;
+};
+
+// Params of a frame over the grid v (fill_params: the resident record or codec
+// volume; vr_render_gmm_baked: the GMM planes); the codec and flexible-block
+// methods add their tables
+int fill_frame_params(const vr_render_desc *d, const FrameVol &v, vr::Params &P, uint32_t &nslots,
+                      bool for_render) {
     const bool codec = d->query_method >= 4 && d->query_method <= 6;
-    if (codec && !g.cb)
-        return fail(VR_ERR_STATE, "queryMethod %d needs a codec volume (initCuda's codebook / "
-                                  "vr_init_codec)", d->query_method);
     const bool flex = is_flex_method(d->query_method);
-    if (!codec && !flex && !g.vol)
-        return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
     if (!d->d_output) return fail(VR_ERR_ARG, "d_output is null");
     if (d->width == 0 || d->height == 0) return fail(VR_ERR_ARG, "empty image");
     int rc = check_method(d->query_method);
@@ -546,11 +561,10 @@ int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
     P.brightness = d->brightness;
     P.toff = d->transfer_offset;
     P.tscale = d->transfer_scale;
-    if (codec) {  // the codec volume: dense voxel order, its own bin count
-        P.nx = g.cnx; P.ny = g.cny; P.nz = g.cnz;
-        P.sy = (uint64_t)g.cnx;
-        P.sz = (uint64_t)g.cnx * (uint64_t)g.cny;
-        P.nb = g.cnb;
+    P.nx = v.nx; P.ny = v.ny; P.nz = v.nz;
+    P.sy = v.sy; P.sz = v.sz;
+    P.nb = v.nb;
+    if (codec) {
         P.cb = g.cb;
         P.tpl = g.tpl;
         P.err = g.cerr;
@@ -560,10 +574,6 @@ int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
         const size_t tb = (size_t)g.ntpl * g.cnb * sizeof(float);
         const char *el = vr::tuning("VR_CODEC_LDS");
         P.tpl_lds = (tb <= 32768 && !(el && std::atoi(el) == 0)) ? (int)tb : 0;
-    } else {
-        P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
-        P.sy = g.sy; P.sz = g.sz;
-        P.nb = g.nb;
     }
     if (flex) {
         P.flex = g.flex.blocks;
@@ -610,6 +620,23 @@ int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
     }
     P.n_tiles = nslots;
     return VR_OK;
+}
+
+int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
+                bool for_render = false) {
+    if (!d) return fail(VR_ERR_ARG, "null render descriptor");
+    const bool codec = d->query_method >= 4 && d->query_method <= 6;
+    if (codec && !g.cb)
+        return fail(VR_ERR_STATE, "queryMethod %d needs a codec volume (initCuda's codebook / "
+                                  "vr_init_codec)", d->query_method);
+    const bool flex = is_flex_method(d->query_method);
+    if (!codec && !flex && !g.vol)
+        return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
+    // the codec volume: dense voxel order, its own bin count
+    const FrameVol v = codec ? FrameVol{g.cnx, g.cny, g.cnz, g.cnb, (uint64_t)g.cnx,
+                                        (uint64_t)g.cnx * (uint64_t)g.cny}
+                             : FrameVol{g.nx, g.ny, g.nz, g.nb, g.sy, g.sz};
+    return fill_frame_params(d, v, P, nslots, for_render);
 }
 
 // Bakes the statistics planes of the resident raw and codec volumes (whichever
@@ -1752,6 +1779,15 @@ void release_all_gmm() {
     g.gmm_slot = 0;
 }
 
+// the baked GMM planes (vr_release_gmm_stats, freeCudaBuffers)
+void release_gmm_stats() {
+    if (g.gstats.buf) {
+        (void)hipFree(g.gstats.buf);
+        g.volume_epoch++;  // a tile order learned on these planes is not reused
+    }
+    g.gstats = State::GmmStats{};
+}
+
 int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
     if (K != 8 && K != 16 && K != 32)
         return fail(VR_ERR_UNSUPPORTED, "GMM volumes with %d components (compiled: 8, 16, 32)", K);
@@ -2098,6 +2134,128 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
     return (int64_t)u;
 }
 
+// The selected slot's resident slices decoded once per voxel into the
+// whole-volume planes (k_bake_gmm, queued on the library stream).  The first
+// call allocates and zeroes the planes; if it fails, nothing has changed.
+int vr_bake_gmm_stats(void) {
+    const State::Gmm &v = g.gmm;
+    if (!v.wm) return fail(VR_ERR_STATE, "no GMM volume resident (vr_init_gmm / vr_synthesize_gmm)");
+    State::GmmStats &b = g.gstats;
+    if (b.buf && (b.nx != v.nx || b.ny != v.ny || b.nz != v.nz))
+        return fail(VR_ERR_STATE, "the GMM planes hold a %d x %d x %d volume, the resident records "
+                    "are of %d x %d x %d: vr_release_gmm_stats first", b.nx, b.ny, b.nz, v.nx, v.ny,
+                    v.nz);
+    if (v.nx > 65535 || v.ny > 65535 || v.nzs > 65535)
+        return fail(VR_ERR_UNSUPPORTED, "baking GMM volumes beyond 65535 voxels per axis");
+    uint64_t psy = b.sy, psz = b.sz, plane = b.plane;
+    float *buf = b.buf;
+    if (!buf) {
+        vr::plane_pitches((uint32_t)v.nx, (uint32_t)v.ny, psy, psz);
+        plane = psz * (uint64_t)v.nz;
+        VR_HIP(hipMalloc(&buf, (2 * plane + 4) * sizeof(float)));
+        // (the planes' padding is read with weight 0: it must hold finite floats)
+        const hipError_t e = hipMemsetAsync(buf, 0, (2 * plane + 4) * sizeof(float), g.stream);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            return hip_fail(e, "vr_bake_gmm_stats(hipMemsetAsync)");
+        }
+    }
+    const hipError_t e = vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base,
+                                             v.nzs, buf, plane, psy, psz, g.stream);
+    if (e != hipSuccess) {
+        if (!b.buf) {  // the planes this call allocated, once their memset has run
+            (void)hipStreamSynchronize(g.stream);
+            (void)hipFree(buf);
+        }
+        return hip_fail(e, "launch(k_bake_gmm)");
+    }
+    if (!b.buf) {
+        b.buf = buf;
+        b.nx = v.nx; b.ny = v.ny; b.nz = v.nz;
+        b.plane = plane;
+        b.sy = psy;
+        b.sz = psz;
+        b.slice.assign((size_t)v.nz, 0);
+        b.nbaked = 0;
+        g.volume_epoch++;
+    }
+    for (int z = v.z_base; z < v.z_base + v.nzs; z++) {
+        b.nbaked += !b.slice[(size_t)z];
+        b.slice[(size_t)z] = 1;
+    }
+    return VR_OK;
+}
+
+int vr_release_gmm_stats(void) {
+    release_gmm_stats();
+    return VR_OK;
+}
+
+int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_floats,
+                      int *slices_baked) {
+    const State::GmmStats &b = g.gstats;
+    if (dims) {
+        dims->width = (size_t)b.nx;
+        dims->height = (size_t)b.ny;
+        dims->depth = (size_t)b.nz;
+    }
+    if (d_planes) *d_planes = b.buf;
+    if (plane_floats) *plane_floats = b.plane;
+    if (slices_baked) *slices_baked = b.nbaked;
+    return VR_OK;
+}
+
+// A frame of method 1 / 2 from the baked GMM planes: vr_render's plane march
+// (plan_march with baked planes and no layout copies) on plane method - 1.
+int vr_render_gmm_baked(const vr_render_desc *desc) {
+    if (!desc) return fail(VR_ERR_ARG, "null render descriptor");
+    const int qm = desc->query_method;
+    if (qm != 1 && qm != 2)
+        return fail(VR_ERR_UNSUPPORTED, "GMM volumes support queryMethod 1 (mean) and 2 (variance)");
+    const State::GmmStats &b = g.gstats;
+    if (!b.buf) return fail(VR_ERR_STATE, "no baked GMM planes (vr_bake_gmm_stats first)");
+    if (b.nbaked != b.nz)
+        return fail(VR_ERR_STATE, "%d of the GMM planes' %d slices are baked", b.nbaked, b.nz);
+    vr::Params P;
+    uint32_t nslots = 0;
+    const FrameVol v = {b.nx, b.ny, b.nz, 1, b.sy, b.sz};
+    int rc = fill_frame_params(desc, v, P, nslots, true);
+    if (rc != VR_OK) return rc;
+    vr::PlanIn in = {};
+    in.m0 = desc->inv_view[0];
+    in.m4 = desc->inv_view[4];
+    in.m8 = desc->inv_view[8];
+    in.W = desc->width;
+    in.H = desc->height;
+    in.CW = P.CW;
+    in.CH = P.CH;
+    in.tile_list = desc->d_tile_list != nullptr;
+    in.n_tiles = desc->n_tiles;
+    in.method = qm;
+    in.nb = 1;
+    in.nx = b.nx;
+    in.ny = b.ny;
+    in.nz = b.nz;
+    in.owned = false;
+    in.f16 = false;
+    in.baked = true;
+    in.plane_sy = b.sy;
+    in.plane_sz = b.sz;
+    in.count = false;
+    // the x-row bricks only: no layout copies of GMM planes
+    in.denied = vr::kLayoutAxis | vr::kLayoutBrick | vr::kLayoutPlane;
+    in.tuning = vr::tuning;
+    const vr::MarchPlan pl = vr::plan_march(in);
+    if (pl.layout != vr::kLayoutNone || pl.method > 0)
+        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of the GMM planes");
+    apply_plan(pl, P);
+    const hipError_t e = vr::launch_plan(pl, b.buf + (uint64_t)(qm - 1) * b.plane, P, nslots,
+                                         g.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch(k_march)");
+    if (P.tile_cost) g.cost_recorded = true;
+    return VR_OK;
+}
+
 // ---------------- reference entry points (K:1889-2406) ------------------
 
 void render_kernel(vr_dim3 gridSize, vr_dim3 blockSize, uint32_t *d_output, uint32_t imageW,
@@ -2210,6 +2368,7 @@ void freeCudaBuffers(void) {
     release_codec();
     release_flex();
     release_all_gmm();
+    release_gmm_stats();
 }
 
 void setTextureFilterMode(bool bLinearFilter) { g.linear_filter = bLinearFilter; }

@@ -158,6 +158,14 @@ __host__ __device__ __forceinline__ uint64_t plane_index(uint32_t x, uint32_t y,
                                                          uint64_t sy, uint64_t sz) {
     return (uint64_t)z * sz + (uint32_t)((y >> 1) * (uint32_t)sy + (y & 1u) * 16u + plane_bx(x));
 }
+// a voxel's statistic at its home position and, for x = 15 k (k > 0), in the
+// apron (offset 15) of brick k - 1 (the bake kernels of vr_stats.hip and vr_gmm.hip)
+__device__ __forceinline__ void put_plane(float *__restrict__ out, uint32_t x, uint32_t y,
+                                          uint32_t z, uint64_t psy, uint64_t psz, float v) {
+    const uint64_t h = plane_index(x, y, z, psy, psz);
+    out[h] = v;
+    if (x > 0 && plane_bx(x) % 32u == 0) out[h - 32u + kPlaneStride] = v;
+}
 
 // Oblique-view copy of a baked plane (round 5): 8 x 2 x 2 bricks -- one 128-B
 // line holds 8 x-neighbours of two y rows and two z slices -- whose x runs

@@ -429,6 +429,92 @@ hipError_t launch_march_gmm(int K, int method, bool half, const Params &P, uint3
                 : launch_gmm_t<false>(K, method, P, nblocks, count, s);
 }
 
+// ---- baked GMM statistics (vr_bake_gmm_stats) ----
+// The mean and the 16 x variance the march decodes at every corner are pure
+// functions of one voxel's record, so one pass over the resident records
+// decodes them once into two float planes in the 16 x 2 x 1 bricks of the
+// histogram volumes' baked planes (plane_index / put_plane, vr_device.h), and a
+// frame is then the plane march of vr_kernels.hip / vr_seg.hip on plane
+// method - 1.  The planes hold the bits gmm_stat<L, 1> and gmm_stat<L, 2>
+// return: the same L = K/4 lanes per voxel, the same partials and DPP sums.
+//
+// A wave takes 64/L consecutive x voxels of one row, a workgroup 4 waves of
+// the same row (grid: x chunks, y rows, resident slices).  Lane s of a group
+// loads components 4s .. 4s + 3, so the wave's loads are contiguous: one row
+// segment of (w, mu) (fp32: 2 x 16 B per lane, f16: 16 B) and one of sigma (16 /
+// 8 B), each record read once for both planes.  The whole group must reach the
+// DPP sums: a lane past the row's end decodes the row's last voxel (clamped
+// address) and skips the store; only a wave wholly past the end leaves.
+// Records are indexed by z - z_base (gmm_vox), the planes by the volume's z.
+template <typename T, int K>
+__global__ __launch_bounds__(256) void k_bake_gmm(const T *__restrict__ wm,
+                                                  const T *__restrict__ sg, uint32_t nx,
+                                                  uint32_t ny, uint32_t z_base,
+                                                  float *__restrict__ out, uint64_t plane,
+                                                  uint64_t psy, uint64_t psz) {
+    constexpr int L = K / 4;              // lanes per voxel
+    constexpr uint32_t R = 64u / L;       // voxels per wave
+    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sub = lane % L;
+    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
+    if (x0 >= nx) return;                 // wave-uniform
+    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
+    const bool in = x < nx;
+    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
+    GmmPart<T, 2> r;
+    GmmPart<T, 1> rm;                     // the same (w, mu): the mean's operand type
+    if constexpr (sizeof(T) == 4) {
+        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
+        r.wm[0] = a[0];
+        r.wm[1] = a[1];
+        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
+        rm.wm[0] = r.wm[0];
+        rm.wm[1] = r.wm[1];
+    } else {
+        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
+        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
+        rm.wm = r.wm;
+    }
+    const float m = gmm_stat<L, 1>(rm);
+    const float v16 = gmm_stat<L, 2>(r);
+    if (in && sub == 0) {
+        const uint32_t z = z_base + zl;
+        put_plane(out, x, y, z, psy, psz, m);
+        put_plane(out + plane, x, y, z, psy, psz, v16);
+    }
+}
+
+template <typename T>
+static hipError_t launch_bake_gmm_t(const T *wm, const T *sg, int K, uint32_t nx, uint32_t ny,
+                                    uint32_t z_base, uint32_t nzs, float *out, uint64_t plane,
+                                    uint64_t psy, uint64_t psz, hipStream_t s) {
+    const uint32_t per_wg = 4u * 64u / (uint32_t)(K / 4);  // voxels of a row per workgroup
+    const dim3 grid((nx + per_wg - 1) / per_wg, ny, nzs), block(256);
+    switch (K) {
+    case 8: hipLaunchKernelGGL((k_bake_gmm<T, 8>), grid, block, 0, s, wm, sg, nx, ny, z_base, out, plane, psy, psz); break;
+    case 16: hipLaunchKernelGGL((k_bake_gmm<T, 16>), grid, block, 0, s, wm, sg, nx, ny, z_base, out, plane, psy, psz); break;
+    case 32: hipLaunchKernelGGL((k_bake_gmm<T, 32>), grid, block, 0, s, wm, sg, nx, ny, z_base, out, plane, psy, psz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_gmm(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                           int z_base, int nzs, float *out, uint64_t plane, uint64_t psy,
+                           uint64_t psz, hipStream_t s) {
+    // (grid y / z: rows and slices; plane_bx: x < 2^16)
+    if (nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 || nzs > 65535)
+        return hipErrorInvalidValue;
+    if (half)
+        return launch_bake_gmm_t(static_cast<const _Float16 *>(wm), static_cast<const _Float16 *>(sg),
+                                 K, (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs,
+                                 out, plane, psy, psz, s);
+    return launch_bake_gmm_t(static_cast<const float *>(wm), static_cast<const float *>(sg), K,
+                             (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, out,
+                             plane, psy, psz, s);
+}
+
 // ---- synthetic GMM volume ----
 // The section-5 blob field f places the mixture: per component k of voxel v
 // (global index x + nx*(y + ny*z)), h = splitmix64(seed ^ 0x6A09E667F3BCC909 ^

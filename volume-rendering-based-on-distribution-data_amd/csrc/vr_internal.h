@@ -99,6 +99,13 @@ hipError_t launch_march_gmm(int K, int method, bool half, const Params &P, uint3
                             bool count, hipStream_t s);
 hipError_t launch_synth_gmm(void *wm, void *sg, bool half, const SynthArgs &a, int K, int z_base,
                             int nzs, hipStream_t s);
+// the resident slices [z_base, z_base + nzs) of an nx x ny GMM volume decoded once
+// per voxel (k_bake_gmm) into two whole-volume planes of `plane` floats at out
+// (mean, then 16 x variance) in 16 x 2 x 1 bricks of pitches psy / psz; nx, ny and
+// nzs beyond 65535: hipErrorInvalidValue
+hipError_t launch_bake_gmm(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                           int z_base, int nzs, float *out, uint64_t plane, uint64_t psy,
+                           uint64_t psz, hipStream_t s);
 // ---- baked statistics (basicDataProcessing, vr_stats.hip): planes of `plane`
 // floats each in 16 x 2 x 1 bricks of plane pitches psy / psz (plane_index),
 // statistic k+1 (raw) / C = k (codec)

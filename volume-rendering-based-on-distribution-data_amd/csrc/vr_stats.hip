@@ -21,15 +21,6 @@
 
 namespace vr {
 
-// a voxel's statistic at its home position and, for x = 15 k (k > 0), in the
-// apron (offset 15) of brick k - 1
-__device__ __forceinline__ void put_plane(float *__restrict__ out, uint32_t x, uint32_t y,
-                                          uint32_t z, uint64_t psy, uint64_t psz, float v) {
-    const uint64_t h = plane_index(x, y, z, psy, psz);
-    out[h] = v;
-    if (x > 0 && plane_bx(x) % 32u == 0) out[h - 32u + kPlaneStride] = v;
-}
-
 // One thread per voxel of an x-row (grid: x blocks of 256, y rows, z slices);
 // each record is read once, coalesced, and its statistics written to the four
 // planes (mean, variance, entropy; plane 3: method 7's undivided corner mean).  The same functions as the march (record_stat), so the

@@ -17,6 +17,10 @@ costs max(PCIe copy, march) per slab plus the first copy; the planes the
 method reads cross PCIe once per frame (method 1: the (w, mu) plane only).  The host waits once per slab for the alive count
 (it sizes the next launch).
 
+GmmStream.bake() instead streams the volume through the same ring once and
+bakes every slab into the library's mean / variance planes (DESIGN.md section
+15); frames are then api.render_gmm_baked, with nothing crossing PCIe.
+
 This module is host logic over the C-ABI (vr_init_gmm adopting the slab
 buffer, vr_render_gmm with a vr_gmm_slab); no device code.
 """
@@ -137,3 +141,39 @@ class GmmStream:
         per_voxel = self.K * (3 if sigma else 2) * self.elem
         return {"slabs": len(bounds), "rays_handed_on": handed,
                 "bytes_streamed": sum(ns for _, ns in res) * self.dims[0] * self.dims[1] * per_voxel}
+
+    def bake(self, stream) -> dict:
+        """One pass over the host volume into the library's baked GMM planes
+        (api.bake_gmm_stats); frames are then
+        api.render_gmm_baked(desc), with no records resident and nothing crossing
+        PCIe.  The same two-buffer ring as render(): slabs of S slices (no halo:
+        a voxel's statistics read its own record only), both planes copied, slab
+        i + 1's copy overlapping slab i's bake on `stream` (also made the
+        library's stream).  Returns the slabs and bytes streamed."""
+        torch = self.torch
+        nz = self.dims[2]
+        bounds = [(z, min(self.S, nz - z)) for z in range(0, nz, self.S)]
+        api.set_stream(stream)
+        stream.wait_stream(torch.cuda.current_stream())
+        self.copy.wait_stream(torch.cuda.current_stream())
+        free = [None, None]
+        copied = [None, None]
+        copied[0] = self._issue_copy(0, bounds[0][0], bounds[0][1], None, True)
+        for i, (zb, ns) in enumerate(bounds):
+            b = i % 2
+            stream.wait_event(copied[b])
+            api.init_gmm(self.dwm[b][:ns], self.dsg[b][:ns], self.dims, z_base=zb, adopt=True)
+            with torch.cuda.stream(stream):
+                api.bake_gmm_stats()
+                done = torch.cuda.Event()
+                done.record(stream)
+            free[b] = done
+            if i + 1 < len(bounds):  # the next slab's copy overlaps this bake
+                nb = (i + 1) % 2
+                copied[nb] = self._issue_copy(nb, bounds[i + 1][0], bounds[i + 1][1], free[nb], True)
+        api.free_gmm()  # the library held an adopted view of a ring buffer
+        # the ring buffers belong to the caller's stream: it passes the last bake
+        torch.cuda.current_stream().wait_stream(stream)
+        per_voxel = self.K * 3 * self.elem
+        return {"slabs": len(bounds),
+                "bytes_streamed": nz * self.dims[0] * self.dims[1] * per_voxel}
