@@ -598,6 +598,56 @@ int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_f
                       int *slices_baked);
 int vr_render_gmm_baked(const vr_render_desc *desc);
 
+/* The weighted-bin query: queryMethod 10 samples
+ * s = sum_i w_i * p_i, a fixed linear functional of a voxel's bins -- the
+ * probability of a value range, the CDF at an isovalue, a tail mass, a custom
+ * moment; only the weights differ.  Arithmetic: float, acc = 0, then for i = 0 ..
+ * B-1 in order acc = acc + p_i * w_i with a separate multiply and add (never
+ * fused), no division or normalisation, subnormal products kept; numpy float32
+ * restates it bit for bit.  Record volumes only (fp32 or f16, owned or adopted)
+ * with 1, 2, 4, 8, 16 or 32 bins; vr_render and render_kernel take the method
+ * like 1/2/3 (tile lists, d_output_f, d_steps, clipped coverage).  Every view
+ * marches the x rows of the records with k_march_lin (vr_last_kernel:
+ * "k_march_lin<B=..,M=10>"); no layout copy is used or made.
+ * vr_render / render_kernel with queryMethod 10: VR_ERR_STATE without a record
+ * volume, without weights, or with a weight count other than the volume's bins;
+ * VR_ERR_UNSUPPORTED for records of any other bin count.  vr_count_footprint
+ * and vr_footprint_bytes: VR_ERR_UNSUPPORTED.
+ *
+ * vr_set_bin_weights: n weights (n in 1, 2, 4, 8, 16, 32, else
+ * VR_ERR_UNSUPPORTED; every weight finite, else VR_ERR_ARG), copied; w == NULL
+ * clears them.  Host state only: no device call, so it works without a GPU and
+ * before any volume is resident.  Setting or clearing weights drops the baked
+ * weighted plane.
+ * vr_bin_weights: the weights (w: room for 32 floats, or NULL) and their count;
+ * VR_ERR_STATE if none are set.
+ * vr_set_query_range: the weights of P(lo <= v < hi) on the normalised value
+ * axis [0, 1], bin i covering [i / n, (i + 1) / n):
+ * w_i = (float)(n * max(0, min(hi, (i + 1) / n) - max(lo, i / n))) evaluated in
+ * double (a fully covered bin: exactly 1).  lo > hi or a non-finite bound:
+ * VR_ERR_ARG; n as for vr_set_bin_weights.
+ *
+ * vr_bake_weighted: the statistic of every voxel, decoded once with the same
+ * arithmetic, into one float plane in the layout of vr_bake_stats (16 x 2 x 1
+ * bricks, the pitches and index formula given at vr_bake_gmm_stats; zeroed
+ * padding).  While the plane is resident a queryMethod-10 frame is rendered from
+ * it by the plane march of vr_render (vr_last_kernel "<B=1,M=0>"; M=-1: a
+ * plane beyond 32-bit indices), bit-identical to the per-step frame.
+ * Synchronous.  VR_ERR_STATE: no record volume, no weights, or a weight count
+ * other than the volume's bins; VR_ERR_UNSUPPORTED: more than 65535 rows or
+ * slices.  The plane is dropped by any change of the weights, a new upload or
+ * release of the volume, vr_convert_f16, vr_release_stats, freeCudaBuffers and
+ * vr_release_weighted.
+ * vr_weighted_info: the plane's device pointer (NULL: not baked) and its length
+ * in floats; either argument may be NULL. */
+#define VR_QUERY_WEIGHTED 10
+int vr_set_bin_weights(const float *w, int n);
+int vr_bin_weights(float *w, int *n);
+int vr_set_query_range(float lo, float hi, int n);
+int vr_bake_weighted(void);
+int vr_release_weighted(void);
+int vr_weighted_info(const float **d_plane, uint64_t *plane_floats);
+
 /* library version string */
 const char *vr_version(void);
 

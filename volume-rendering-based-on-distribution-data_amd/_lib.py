@@ -20,6 +20,7 @@ VR_ERR_HIP = -3
 VR_ERR_UNSUPPORTED = -4
 VR_DTYPE_F32 = 0
 VR_DTYPE_F16 = 1
+VR_QUERY_WEIGHTED = 10
 
 
 class VRError(RuntimeError):
@@ -104,6 +105,8 @@ EXPORTS = [
     "vr_layout_info", "vr_init_distribution_f16", "vr_convert_f16", "vr_volume_dtype",
     "vr_init_gmm_f16", "vr_synthesize_gmm_f16", "vr_convert_gmm_f16", "vr_gmm_dtype",
     "vr_bake_gmm_stats", "vr_release_gmm_stats", "vr_gmm_stats_info", "vr_render_gmm_baked",
+    "vr_set_bin_weights", "vr_bin_weights", "vr_set_query_range", "vr_bake_weighted",
+    "vr_release_weighted", "vr_weighted_info",
 ]
 
 _lib = None
@@ -242,6 +245,18 @@ def load() -> ctypes.CDLL:
     L.vr_gmm_stats_info.restype = i32
     L.vr_render_gmm_baked.argtypes = [ctypes.POINTER(RenderDesc)]
     L.vr_render_gmm_baked.restype = i32
+    L.vr_set_bin_weights.argtypes = [vp, i32]
+    L.vr_set_bin_weights.restype = i32
+    L.vr_bin_weights.argtypes = [vp, vp]
+    L.vr_bin_weights.restype = i32
+    L.vr_set_query_range.argtypes = [f32, f32, i32]
+    L.vr_set_query_range.restype = i32
+    L.vr_bake_weighted.argtypes = []
+    L.vr_bake_weighted.restype = i32
+    L.vr_release_weighted.argtypes = []
+    L.vr_release_weighted.restype = i32
+    L.vr_weighted_info.argtypes = [vp] * 2
+    L.vr_weighted_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

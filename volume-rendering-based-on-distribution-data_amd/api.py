@@ -617,6 +617,74 @@ def render_gmm_baked(desc: RenderDesc) -> None:
     check(_lib.load().vr_render_gmm_baked(ctypes.byref(desc)))
 
 
+# --------------------------------- weighted-bin query (method 10)
+
+QUERY_WEIGHTED = _lib.VR_QUERY_WEIGHTED
+
+
+def range_weights(lo: float, hi: float, n: int) -> np.ndarray:
+    """The bin weights of the range probability P(lo <= v < hi) on the normalised
+    value axis [0, 1], bin i covering [i / n, (i + 1) / n):
+    w_i = n * max(0, min(hi, (i + 1) / n) - max(lo, i / n)) in float64, rounded to
+    float32 -- vr_set_query_range's formula restated (a pure function: no library
+    is loaded).  The bounds are first rounded to float32, as the C call takes them."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n must be >= 1, got {n}")
+    lo, hi = np.float64(np.float32(lo)), np.float64(np.float32(hi))
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+        raise ValueError("bounds must be finite with lo <= hi")
+    i = np.arange(n, dtype=np.float64)
+    a = np.maximum(lo, i / np.float64(n))
+    b = np.minimum(hi, (i + 1.0) / np.float64(n))
+    return (np.float64(n) * np.maximum(0.0, b - a)).astype(np.float32)
+
+
+def set_bin_weights(w) -> None:
+    """Set the weights of query method 10, s = sum w_i p_i (1, 2, 4, 8, 16 or 32
+    finite floats, one per bin of the record volume); None clears them.  Host
+    state only; a baked weighted plane is dropped."""
+    L = _lib.load()
+    if w is None:
+        check(L.vr_set_bin_weights(None, 0))
+        return
+    a = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))
+    check(L.vr_set_bin_weights(a.ctypes.data, int(a.size)))
+
+
+def bin_weights() -> np.ndarray:
+    """The weights set (float32 array); VRError (VR_ERR_STATE) if none are."""
+    w = np.zeros(32, np.float32)
+    n = ctypes.c_int()
+    check(_lib.load().vr_bin_weights(w.ctypes.data, ctypes.addressof(n)))
+    return w[:n.value].copy()
+
+
+def set_query_range(lo: float, hi: float, n: int) -> None:
+    """Set the weights of the range probability P(lo <= v < hi) for n-bin records
+    (vr_set_query_range; range_weights(lo, hi, n) gives the same floats)."""
+    check(_lib.load().vr_set_query_range(float(lo), float(hi), int(n)))
+
+
+def bake_weighted() -> None:
+    """Decode the weighted statistic of every voxel once into a float plane
+    (vr_bake_weighted, synchronous); method-10 frames then read the plane,
+    bit-identical to the per-step frames, until the weights or the volume change."""
+    check(_lib.load().vr_bake_weighted())
+
+
+def release_weighted() -> None:
+    """Drop the baked weighted plane: method 10 decodes the records per step again."""
+    check(_lib.load().vr_release_weighted())
+
+
+def weighted_info():
+    """(plane_ptr, plane_floats) of the baked weighted plane; plane_ptr None = not baked"""
+    p, n = ctypes.c_void_p(), ctypes.c_uint64()
+    check(_lib.load().vr_weighted_info(ctypes.addressof(p), ctypes.addressof(n)))
+    return p.value, n.value
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -632,5 +700,7 @@ __all__ = [
     "gmm_count_footprint", "bake_stats", "release_stats", "stats_info", "set_layout_budget",
     "layout_info", "convert_f16", "volume_dtype", "convert_gmm_f16", "gmm_dtype",
     "bake_gmm_stats", "release_gmm_stats", "gmm_stats_info", "render_gmm_baked",
+    "QUERY_WEIGHTED", "range_weights", "set_bin_weights", "bin_weights", "set_query_range",
+    "bake_weighted", "release_weighted", "weighted_info",
     "VRError", "PAD",
 ]

@@ -91,6 +91,14 @@ struct State {
     float *stats = nullptr, *cstats = nullptr;
     uint64_t stats_plane = 0, cstats_plane = 0;
     uint64_t stats_sy = 0, stats_sz = 0, cstats_sy = 0, cstats_sz = 0;  // plane_pitches
+    // weighted-bin query (method 10, vr_query.hip): the bin
+    // weights (qn = 0: none set; host state, no HIP call sets or reads them) and
+    // the plane vr_bake_weighted made of them (nullptr: the march decodes per
+    // step), wplane floats in the bricks of pitches wsy / wsz
+    vr::BinWeights qw = {};
+    int qn = 0;
+    float *wstats = nullptr;
+    uint64_t wplane = 0, wsy = 0, wsz = 0;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -154,8 +162,20 @@ int hip_fail(hipError_t e, const char *what) {
 
 void release_plane_copies();
 
+// the baked weighted plane (vr_release_weighted; with the records' other planes;
+// on any change of the weights)
+void release_weighted() {
+    if (g.wstats) {
+        (void)hipFree(g.wstats);
+        g.volume_epoch++;  // a tile order learned on the plane march is not reused
+    }
+    g.wstats = nullptr;
+    g.wplane = 0;
+}
+
 void release_stats() {
     release_plane_copies();  // copies of the planes go with them
+    release_weighted();      // derived from the same records
     if (g.stats) (void)hipFree(g.stats);
     g.stats = nullptr;
     g.stats_plane = 0;
@@ -301,8 +321,25 @@ void release_flex() {
 
 bool is_flex_method(int m) { return m == 8 || m == 9 || m == 0; }
 
+bool lin_bins(int n) { return n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 32; }
+
 int check_method(int m) {
     if (m == 1 || m == 2 || m == 3 || m == 7 || m == 4 || m == 5 || m == 6) return VR_OK;
+    if (m == VR_QUERY_WEIGHTED) {
+        if (!g.vol)
+            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
+                                      "vr_init_distribution*)", m);
+        if (!lin_bins(g.nb))
+            return fail(VR_ERR_UNSUPPORTED, "the weighted-bin query on records of %d bins "
+                                            "(compiled: 1,2,4,8,16,32)", g.nb);
+        if (g.qn == 0)
+            return fail(VR_ERR_STATE, "queryMethod %d needs bin weights (vr_set_bin_weights / "
+                                      "vr_set_query_range)", m);
+        if (g.qn != g.nb)
+            return fail(VR_ERR_STATE, "%d bin weights are set, the resident records have %d bins",
+                        g.qn, g.nb);
+        return VR_OK;
+    }
     if (is_flex_method(m)) {
         if (!g.flex.blocks)
             return fail(VR_ERR_STATE,
@@ -1557,6 +1594,52 @@ void apply_plan(const vr::MarchPlan &pl, vr::Params &P) {
     P.wg_per_cu = pl.wg_per_cu;
 }
 
+// The march of a weighted-bin frame (method 10; check_method has passed).  Per
+// step: k_march_lin on the x rows of the records, whatever the view -- no plan, no
+// layout copy.  With the baked plane resident (vr_bake_weighted): the plane march
+// plan_march names for one float per voxel in x-row bricks, the route of
+// vr_render_gmm_baked -- the same eight floats into the same filter, so the same
+// frame bit for bit.
+int launch_weighted(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
+    if (!g.wstats) {
+        e = vr::launch_march_lin(g.vol, is_f16(), P, g.qw, nslots, g.stream);
+        return VR_OK;
+    }
+    vr::PlanIn in = {};
+    in.m0 = desc->inv_view[0];
+    in.m4 = desc->inv_view[4];
+    in.m8 = desc->inv_view[8];
+    in.W = desc->width;
+    in.H = desc->height;
+    in.CW = P.CW;
+    in.CH = P.CH;
+    in.tile_list = desc->d_tile_list != nullptr;
+    in.n_tiles = desc->n_tiles;
+    in.method = 1;  // any plane statistic: the plan of a baked frame reads no more of it
+    in.nb = 1;
+    in.nx = g.nx;
+    in.ny = g.ny;
+    in.nz = g.nz;
+    in.owned = false;
+    in.f16 = false;
+    in.baked = true;
+    in.plane_sy = g.wsy;
+    in.plane_sz = g.wsz;
+    in.count = false;
+    // the x-row bricks only: no layout copies of the weighted plane
+    in.denied = vr::kLayoutAxis | vr::kLayoutBrick | vr::kLayoutPlane;
+    in.tuning = vr::tuning;
+    const vr::MarchPlan pl = vr::plan_march(in);
+    if (pl.layout != vr::kLayoutNone || pl.method > 0)
+        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of the weighted plane");
+    apply_plan(pl, P);
+    P.nb = 1;
+    P.sy = g.wsy;
+    P.sz = g.wsz;
+    e = vr::launch_plan(pl, g.wstats, P, nslots, g.stream);
+    return VR_OK;
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -1596,6 +1679,10 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
         if (e == hipErrorInvalidValue)
             return fail(VR_ERR_UNSUPPORTED, "codec volumes with %d bins (compiled: 1,2,4,8,16,32)",
                         P.nb);
+    } else if (qm == VR_QUERY_WEIGHTED) {
+        if (dry) return VR_OK;
+        rc = launch_weighted(desc, P, nslots, e);
+        if (rc != VR_OK) return rc;
     } else {
         // records (fp32 / f16) and baked planes: vr_plan.cpp chooses the march
         if (qm == 7 && is_f16() && !g.stats)
@@ -1684,6 +1771,8 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
+    if (desc && desc->query_method == VR_QUERY_WEIGHTED)  // no counting instance of k_march_lin
+        return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
     uint32_t nslots = 0;
     int rc = fill_params(desc, P, nslots);
@@ -1712,6 +1801,8 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
+    if (desc && desc->query_method == VR_QUERY_WEIGHTED)
+        return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
     uint32_t nslots = 0;
     int rc = fill_params(desc, P, nslots);
@@ -2387,6 +2478,98 @@ int vr_release_stats(void) {
     release_cstats();
     release_brick();  // the layout copies are derived from the records too
     release_axis_copy();
+    return VR_OK;
+}
+
+// ---------------- weighted-bin query (method 10) ----------
+
+int vr_set_bin_weights(const float *w, int n) {
+    if (!w) {  // clear
+        release_weighted();
+        g.qn = 0;
+        g.qw = vr::BinWeights{};
+        return VR_OK;
+    }
+    if (!lin_bins(n))
+        return fail(VR_ERR_UNSUPPORTED, "%d bin weights (supported: 1,2,4,8,16,32)", n);
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(w[i])) return fail(VR_ERR_ARG, "bin weight %d is not finite", i);
+    release_weighted();  // a plane baked with other weights
+    g.qw = vr::BinWeights{};
+    std::memcpy(g.qw.w, w, (size_t)n * sizeof(float));
+    g.qn = n;
+    return VR_OK;
+}
+
+int vr_bin_weights(float *w, int *n) {
+    if (g.qn == 0) return fail(VR_ERR_STATE, "no bin weights set");
+    if (w) std::memcpy(w, g.qw.w, (size_t)g.qn * sizeof(float));
+    if (n) *n = g.qn;
+    return VR_OK;
+}
+
+int vr_set_query_range(float lo, float hi, int n) {
+    if (!lin_bins(n))
+        return fail(VR_ERR_UNSUPPORTED, "%d bin weights (supported: 1,2,4,8,16,32)", n);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi)
+        return fail(VR_ERR_ARG, "vr_set_query_range: bounds must be finite with lo <= hi");
+    float w[32];
+    const double l = (double)lo, h = (double)hi, dn = (double)n;
+    for (int i = 0; i < n; i++) {  // the part of [lo, hi) inside bin i, in bin widths
+        const double a = std::max(l, (double)i / dn), b = std::min(h, ((double)i + 1.0) / dn);
+        w[i] = (float)(dn * std::max(0.0, b - a));
+    }
+    return vr_set_bin_weights(w, n);
+}
+
+int vr_bake_weighted(void) {
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
+    if (g.qn == 0)
+        return fail(VR_ERR_STATE, "no bin weights set (vr_set_bin_weights / vr_set_query_range)");
+    if (g.qn != g.nb)
+        return fail(VR_ERR_STATE, "%d bin weights are set, the resident records have %d bins", g.qn,
+                    g.nb);
+    if (g.wstats) return VR_OK;  // baked with these weights: any change drops the plane
+    vr::Params P;
+    std::memset(&P, 0, sizeof P);
+    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
+    P.sy = g.sy; P.sz = g.sz;
+    P.nb = g.nb;
+    uint64_t psy = 0, psz = 0;
+    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
+    const uint64_t plane = psz * (uint64_t)g.nz;
+    float *buf = nullptr;
+    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
+    // (the plane's padding is read with weight 0: it must hold finite floats)
+    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
+    if (e == hipSuccess)
+        e = vr::launch_bake_lin(g.vol, is_f16(), P, g.qw, buf, psy, psz, g.stream);
+    // synchronous, like vr_bake_stats: a later frame may run on another stream
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(g.stream);
+        (void)hipFree(buf);
+        if (e == hipErrorInvalidValue)
+            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
+                                            "slices)", g.nx, g.ny, g.nz);
+        return hip_fail(e, "vr_bake_weighted(k_bake_lin)");
+    }
+    g.wstats = buf;
+    g.wplane = plane;
+    g.wsy = psy;
+    g.wsz = psz;
+    g.volume_epoch++;
+    return VR_OK;
+}
+
+int vr_release_weighted(void) {
+    release_weighted();
+    return VR_OK;
+}
+
+int vr_weighted_info(const float **d_plane, uint64_t *plane_floats) {
+    if (d_plane) *d_plane = g.wstats;
+    if (plane_floats) *plane_floats = g.wplane;
     return VR_OK;
 }
 

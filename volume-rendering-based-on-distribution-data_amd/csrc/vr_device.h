@@ -582,6 +582,21 @@ __device__ __forceinline__ float record_stat(const float (&p)[B], float enorm) {
     }
 }
 
+// The weighted-bin query (method 10): a fixed linear
+// functional of the bins, s = sum w_i p_i, in float -- one multiply and one add
+// per bin in bin order, never fused (numpy float32 restates it bit for bit),
+// no division, subnormal products kept.  w: B weights, uniform over the launch.
+template <int B>
+__device__ __forceinline__ float lin_stat(const float (&p)[B], const float *w) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < B; i++) {
+        const float t = p[i] * w[i];
+        acc = acc + t;
+    }
+    return acc;
+}
+
 // record_stat with the entropy's log table in LDS (tab: copy_logtab)
 template <int B, int M>
 __device__ __forceinline__ float record_stat_p(const float (&p)[B], float enorm, const LogEnt *tab) {

@@ -140,6 +140,22 @@ hipError_t launch_stream_read(const void *buf, uint64_t bytes, uint32_t *out, ui
 // nb in 1, 2, 4, 8, 16, 32), launch_march_h above ----
 // n floats at src narrowed to n halves at dst (round to nearest even, subnormals kept)
 hipError_t launch_narrow_f16(const float *src, void *dst, uint64_t n, hipStream_t s);
+// ---- weighted-bin query (method 10, vr_query.hip) ----
+// the bin weights of a launch: a kernel argument of their own after Params
+// (wave-uniform kernarg: scalar loads, SGPR operands of the multiplies); the
+// first nb entries are used
+struct BinWeights {
+    float w[32];
+};
+// k_march_lin: the per-ray pipelined march of sum w_i p_i over the x rows of the
+// records (half: binary16), P.nb in 1, 2, 4, 8, 16, 32 (hipErrorInvalidValue
+// otherwise); records its name for vr_last_kernel()
+hipError_t launch_march_lin(const void *vol, bool half, const Params &P, const BinWeights &w,
+                            uint32_t nslots, hipStream_t s);
+// k_bake_lin: the same statistic of every voxel into one float plane at out, in
+// the 16 x 2 x 1 bricks of pitches psy / psz (launch_bake_raw's layout and limits)
+hipError_t launch_bake_lin(const void *vol, bool half, const Params &P, const BinWeights &w,
+                           float *out, uint64_t psy, uint64_t psz, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
