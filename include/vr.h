@@ -648,6 +648,58 @@ int vr_bake_weighted(void);
 int vr_release_weighted(void);
 int vr_weighted_info(const float **d_plane, uint64_t *plane_floats);
 
+/* The quantile query: queryMethod 11 samples the inverse
+ * of a voxel's CDF -- s = Q(q), the value on the normalised axis [0, 1] where the
+ * CDF reaches q (the median, a percentile), or the spread s = Q(q_hi) - Q(q_lo)
+ * (the interquartile range).  Bin i covers [i / B, (i + 1) / B) with its mass
+ * spread uniformly, the conventions of vr_set_query_range.  Arithmetic: float,
+ *   c_-1 = 0, c_i = c_{i-1} + p_i for i = 0 .. B-1 in order; T = c_{B-1};
+ *   tau = q * T; k = the smallest i with c_i >= tau and p_i > 0, B-1 if none;
+ *   frac = p_k > 0 ? (tau - c_{k-1}) / p_k : 0 (a correctly rounded IEEE division,
+ *   subnormal quotients kept), then frac > 0 ? (frac > 1 ? 1 : frac) : 0;
+ *   Q = (k + frac) * (1 / B); Q = T > 0 ? Q : 0 (an empty record: 0);
+ * the spread is one float subtraction of two such values taken from the same
+ * prefix sums.  The record is not normalised; Q(0) is the lower edge of its
+ * support and Q(1) the upper edge; a record with negative bins gets whatever
+ * these lines give.  numpy float32 restates it bit for bit.  Record volumes only
+ * (fp32 or f16, owned or adopted) with 1, 2, 4, 8, 16 or 32 bins; vr_render and
+ * render_kernel take the method like 1/2/3/10 (tile lists, d_output_f, d_steps,
+ * clipped coverage).  Every view marches the x rows of the records with
+ * k_march_quant (vr_last_kernel: "k_march_quant<B=..,M=11>"); no layout copy is
+ * used or made.
+ * vr_render / render_kernel with queryMethod 11: VR_ERR_STATE without a record
+ * volume or without a quantile set; VR_ERR_UNSUPPORTED for records of any other
+ * bin count.  vr_count_footprint and vr_footprint_bytes: VR_ERR_UNSUPPORTED.
+ *
+ * vr_set_quantile: a single quantile q.  vr_set_quantile_spread: the spread
+ * between q_lo and q_hi.  q finite and in [0, 1], q_lo <= q_hi, else VR_ERR_ARG
+ * and the state stays as it was.  Host state only: no device call, so they work
+ * without a GPU and before any volume is resident.  vr_clear_quantile: none set.
+ * Each of the three drops the baked quantile plane.
+ * vr_quantile: what is set (a single quantile: *q_lo == *q_hi, *spread = 0; the
+ * spread: *spread = 1); any argument may be NULL; VR_ERR_STATE if none is set.
+ *
+ * vr_bake_quantile: the statistic of every voxel, decoded once with the same
+ * arithmetic, into one float plane in the layout of vr_bake_stats (as
+ * vr_bake_weighted; a plane of its own, resident beside the weighted plane or
+ * without it).  While it is resident a queryMethod-11 frame is rendered from it
+ * by the plane march of vr_render (vr_last_kernel "<B=1,M=0>"; M=-1: a plane
+ * beyond 32-bit indices), bit-identical to the per-step frame.  Synchronous.
+ * VR_ERR_STATE: no record volume or no quantile set; VR_ERR_UNSUPPORTED: another
+ * bin count, more than 65535 rows or slices.  The plane is dropped by any call
+ * that sets or clears the quantile, a new upload or release of the volume,
+ * vr_convert_f16, vr_release_stats, freeCudaBuffers and vr_release_quantile.
+ * vr_quantile_info: the plane's device pointer (NULL: not baked) and its length
+ * in floats; either argument may be NULL. */
+#define VR_QUERY_QUANTILE 11
+int vr_set_quantile(float q);
+int vr_set_quantile_spread(float q_lo, float q_hi);
+int vr_clear_quantile(void);
+int vr_quantile(float *q_lo, float *q_hi, int *spread);
+int vr_bake_quantile(void);
+int vr_release_quantile(void);
+int vr_quantile_info(const float **d_plane, uint64_t *plane_floats);
+
 /* library version string */
 const char *vr_version(void);
 

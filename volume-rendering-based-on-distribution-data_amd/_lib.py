@@ -21,6 +21,7 @@ VR_ERR_UNSUPPORTED = -4
 VR_DTYPE_F32 = 0
 VR_DTYPE_F16 = 1
 VR_QUERY_WEIGHTED = 10
+VR_QUERY_QUANTILE = 11
 
 
 class VRError(RuntimeError):
@@ -107,6 +108,8 @@ EXPORTS = [
     "vr_bake_gmm_stats", "vr_release_gmm_stats", "vr_gmm_stats_info", "vr_render_gmm_baked",
     "vr_set_bin_weights", "vr_bin_weights", "vr_set_query_range", "vr_bake_weighted",
     "vr_release_weighted", "vr_weighted_info",
+    "vr_set_quantile", "vr_set_quantile_spread", "vr_clear_quantile", "vr_quantile",
+    "vr_bake_quantile", "vr_release_quantile", "vr_quantile_info",
 ]
 
 _lib = None
@@ -257,6 +260,20 @@ def load() -> ctypes.CDLL:
     L.vr_release_weighted.restype = i32
     L.vr_weighted_info.argtypes = [vp] * 2
     L.vr_weighted_info.restype = i32
+    L.vr_set_quantile.argtypes = [f32]
+    L.vr_set_quantile.restype = i32
+    L.vr_set_quantile_spread.argtypes = [f32, f32]
+    L.vr_set_quantile_spread.restype = i32
+    L.vr_clear_quantile.argtypes = []
+    L.vr_clear_quantile.restype = i32
+    L.vr_quantile.argtypes = [vp] * 3
+    L.vr_quantile.restype = i32
+    L.vr_bake_quantile.argtypes = []
+    L.vr_bake_quantile.restype = i32
+    L.vr_release_quantile.argtypes = []
+    L.vr_release_quantile.restype = i32
+    L.vr_quantile_info.argtypes = [vp] * 2
+    L.vr_quantile_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

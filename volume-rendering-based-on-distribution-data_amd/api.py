@@ -685,6 +685,53 @@ def weighted_info():
     return p.value, n.value
 
 
+# --------------------------------- quantile query (method 11)
+
+QUERY_QUANTILE = _lib.VR_QUERY_QUANTILE
+
+
+def set_quantile(q) -> None:
+    """Set query method 11 to the quantile Q(q), the value on the normalised axis
+    [0, 1] where a voxel's CDF reaches q (0.5: the median); None clears it.  Host
+    state only; a baked quantile plane is dropped."""
+    L = _lib.load()
+    check(L.vr_clear_quantile() if q is None else L.vr_set_quantile(float(q)))
+
+
+def set_quantile_spread(lo: float, hi: float) -> None:
+    """Set query method 11 to the spread Q(hi) - Q(lo) (0.25, 0.75: the
+    interquartile range); 0 <= lo <= hi <= 1."""
+    check(_lib.load().vr_set_quantile_spread(float(lo), float(hi)))
+
+
+def quantile():
+    """(q_lo, q_hi, spread) as set (a single quantile: q_lo == q_hi, spread False);
+    VRError (VR_ERR_STATE) if none is."""
+    lo, hi, sp = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+    check(_lib.load().vr_quantile(ctypes.addressof(lo), ctypes.addressof(hi),
+                                  ctypes.addressof(sp)))
+    return lo.value, hi.value, bool(sp.value)
+
+
+def bake_quantile() -> None:
+    """Decode the quantile statistic of every voxel once into a float plane
+    (vr_bake_quantile, synchronous); method-11 frames then read the plane,
+    bit-identical to the per-step frames, until the quantile or the volume change."""
+    check(_lib.load().vr_bake_quantile())
+
+
+def release_quantile() -> None:
+    """Drop the baked quantile plane: method 11 decodes the records per step again."""
+    check(_lib.load().vr_release_quantile())
+
+
+def quantile_info():
+    """(plane_ptr, plane_floats) of the baked quantile plane; plane_ptr None = not baked"""
+    p, n = ctypes.c_void_p(), ctypes.c_uint64()
+    check(_lib.load().vr_quantile_info(ctypes.addressof(p), ctypes.addressof(n)))
+    return p.value, n.value
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -702,5 +749,7 @@ __all__ = [
     "bake_gmm_stats", "release_gmm_stats", "gmm_stats_info", "render_gmm_baked",
     "QUERY_WEIGHTED", "range_weights", "set_bin_weights", "bin_weights", "set_query_range",
     "bake_weighted", "release_weighted", "weighted_info",
+    "QUERY_QUANTILE", "set_quantile", "set_quantile_spread", "quantile", "bake_quantile",
+    "release_quantile", "quantile_info",
     "VRError", "PAD",
 ]

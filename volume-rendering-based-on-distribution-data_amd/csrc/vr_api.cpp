@@ -99,6 +99,13 @@ struct State {
     int qn = 0;
     float *wstats = nullptr;
     uint64_t wplane = 0, wsy = 0, wsz = 0;
+    // quantile query (method 11, vr_quantile.hip): the
+    // quantiles (qmode 0: none set, 1: Q(q_lo), 2: the spread Q(q_hi) - Q(q_lo);
+    // host state) and the plane vr_bake_quantile made of them, a plane of its own
+    vr::QuantArgs qq = {};
+    int qmode = 0;
+    float *qstats = nullptr;
+    uint64_t qplane = 0, qsy = 0, qsz = 0;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -173,9 +180,21 @@ void release_weighted() {
     g.wplane = 0;
 }
 
+// the baked quantile plane (vr_release_quantile; with the records' other planes;
+// on any call that sets or clears the quantile)
+void release_quantile() {
+    if (g.qstats) {
+        (void)hipFree(g.qstats);
+        g.volume_epoch++;
+    }
+    g.qstats = nullptr;
+    g.qplane = 0;
+}
+
 void release_stats() {
     release_plane_copies();  // copies of the planes go with them
     release_weighted();      // derived from the same records
+    release_quantile();
     if (g.stats) (void)hipFree(g.stats);
     g.stats = nullptr;
     g.stats_plane = 0;
@@ -338,6 +357,18 @@ int check_method(int m) {
         if (g.qn != g.nb)
             return fail(VR_ERR_STATE, "%d bin weights are set, the resident records have %d bins",
                         g.qn, g.nb);
+        return VR_OK;
+    }
+    if (m == VR_QUERY_QUANTILE) {
+        if (!g.vol)
+            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
+                                      "vr_init_distribution*)", m);
+        if (!lin_bins(g.nb))
+            return fail(VR_ERR_UNSUPPORTED, "the quantile query on records of %d bins "
+                                            "(compiled: 1,2,4,8,16,32)", g.nb);
+        if (g.qmode == 0)
+            return fail(VR_ERR_STATE, "queryMethod %d needs a quantile (vr_set_quantile / "
+                                      "vr_set_quantile_spread)", m);
         return VR_OK;
     }
     if (is_flex_method(m)) {
@@ -1594,17 +1625,10 @@ void apply_plan(const vr::MarchPlan &pl, vr::Params &P) {
     P.wg_per_cu = pl.wg_per_cu;
 }
 
-// The march of a weighted-bin frame (method 10; check_method has passed).  Per
-// step: k_march_lin on the x rows of the records, whatever the view -- no plan, no
-// layout copy.  With the baked plane resident (vr_bake_weighted): the plane march
-// plan_march names for one float per voxel in x-row bricks, the route of
-// vr_render_gmm_baked -- the same eight floats into the same filter, so the same
-// frame bit for bit.
-int launch_weighted(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
-    if (!g.wstats) {
-        e = vr::launch_march_lin(g.vol, is_f16(), P, g.qw, nslots, g.stream);
-        return VR_OK;
-    }
+// a frame from a plane of one float per voxel baked from the records (the
+// weighted plane, the quantile plane) in x-row bricks of pitches psy / psz
+int launch_record_plane(const vr_render_desc *desc, vr::Params &P, uint32_t nslots,
+                        const float *plane, uint64_t psy, uint64_t psz, hipError_t &e) {
     vr::PlanIn in = {};
     in.m0 = desc->inv_view[0];
     in.m4 = desc->inv_view[4];
@@ -1623,21 +1647,46 @@ int launch_weighted(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, 
     in.owned = false;
     in.f16 = false;
     in.baked = true;
-    in.plane_sy = g.wsy;
-    in.plane_sz = g.wsz;
+    in.plane_sy = psy;
+    in.plane_sz = psz;
     in.count = false;
-    // the x-row bricks only: no layout copies of the weighted plane
+    // the x-row bricks only: no layout copies of such a plane
     in.denied = vr::kLayoutAxis | vr::kLayoutBrick | vr::kLayoutPlane;
     in.tuning = vr::tuning;
     const vr::MarchPlan pl = vr::plan_march(in);
     if (pl.layout != vr::kLayoutNone || pl.method > 0)
-        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of the weighted plane");
+        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of a baked query plane");
     apply_plan(pl, P);
     P.nb = 1;
-    P.sy = g.wsy;
-    P.sz = g.wsz;
-    e = vr::launch_plan(pl, g.wstats, P, nslots, g.stream);
+    P.sy = psy;
+    P.sz = psz;
+    e = vr::launch_plan(pl, plane, P, nslots, g.stream);
     return VR_OK;
+}
+
+// The march of a weighted-bin frame (method 10; check_method has passed).  Per
+// step: k_march_lin on the x rows of the records, whatever the view -- no plan, no
+// layout copy.  With the baked plane resident (vr_bake_weighted): the plane march
+// plan_march names for one float per voxel in x-row bricks, the route of
+// vr_render_gmm_baked -- the same eight floats into the same filter, so the same
+// frame bit for bit.
+int launch_weighted(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
+    if (!g.wstats) {
+        e = vr::launch_march_lin(g.vol, is_f16(), P, g.qw, nslots, g.stream);
+        return VR_OK;
+    }
+    return launch_record_plane(desc, P, nslots, g.wstats, g.wsy, g.wsz, e);
+}
+
+// The march of a quantile frame (method 11; check_method has passed), shaped like
+// launch_weighted: k_march_quant per step, the plane march once vr_bake_quantile
+// has made the plane.
+int launch_quantile(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
+    if (!g.qstats) {
+        e = vr::launch_march_quant(g.vol, is_f16(), P, g.qq, g.qmode == 2, nslots, g.stream);
+        return VR_OK;
+    }
+    return launch_record_plane(desc, P, nslots, g.qstats, g.qsy, g.qsz, e);
 }
 
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
@@ -1682,6 +1731,10 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     } else if (qm == VR_QUERY_WEIGHTED) {
         if (dry) return VR_OK;
         rc = launch_weighted(desc, P, nslots, e);
+        if (rc != VR_OK) return rc;
+    } else if (qm == VR_QUERY_QUANTILE) {
+        if (dry) return VR_OK;
+        rc = launch_quantile(desc, P, nslots, e);
         if (rc != VR_OK) return rc;
     } else {
         // records (fp32 / f16) and baked planes: vr_plan.cpp chooses the march
@@ -1771,7 +1824,8 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
-    if (desc && desc->query_method == VR_QUERY_WEIGHTED)  // no counting instance of k_march_lin
+    if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||  // no counting instance of
+                 desc->query_method == VR_QUERY_QUANTILE))   // k_march_lin / k_march_quant
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
     uint32_t nslots = 0;
@@ -1801,7 +1855,8 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
-    if (desc && desc->query_method == VR_QUERY_WEIGHTED)
+    if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||
+                 desc->query_method == VR_QUERY_QUANTILE))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
     uint32_t nslots = 0;
@@ -2570,6 +2625,96 @@ int vr_release_weighted(void) {
 int vr_weighted_info(const float **d_plane, uint64_t *plane_floats) {
     if (d_plane) *d_plane = g.wstats;
     if (plane_floats) *plane_floats = g.wplane;
+    return VR_OK;
+}
+
+// ---------------- quantile query (method 11) ----------------
+
+namespace {
+bool quantile_ok(float q) { return std::isfinite(q) && q >= 0.0f && q <= 1.0f; }
+}  // namespace
+
+int vr_set_quantile(float q) {
+    if (!quantile_ok(q)) return fail(VR_ERR_ARG, "vr_set_quantile: q must be in [0, 1]");
+    release_quantile();  // a plane baked for another quantile
+    g.qq = vr::QuantArgs{q, q};
+    g.qmode = 1;
+    return VR_OK;
+}
+
+int vr_set_quantile_spread(float q_lo, float q_hi) {
+    if (!quantile_ok(q_lo) || !quantile_ok(q_hi) || q_lo > q_hi)
+        return fail(VR_ERR_ARG, "vr_set_quantile_spread: 0 <= q_lo <= q_hi <= 1 required");
+    release_quantile();
+    g.qq = vr::QuantArgs{q_lo, q_hi};
+    g.qmode = 2;
+    return VR_OK;
+}
+
+int vr_clear_quantile(void) {
+    release_quantile();
+    g.qq = vr::QuantArgs{};
+    g.qmode = 0;
+    return VR_OK;
+}
+
+int vr_quantile(float *q_lo, float *q_hi, int *spread) {
+    if (g.qmode == 0) return fail(VR_ERR_STATE, "no quantile set");
+    if (q_lo) *q_lo = g.qq.q_lo;
+    if (q_hi) *q_hi = g.qq.q_hi;
+    if (spread) *spread = g.qmode == 2;
+    return VR_OK;
+}
+
+int vr_bake_quantile(void) {
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
+    if (g.qmode == 0)
+        return fail(VR_ERR_STATE, "no quantile set (vr_set_quantile / vr_set_quantile_spread)");
+    if (!lin_bins(g.nb))
+        return fail(VR_ERR_UNSUPPORTED, "the quantile query on records of %d bins "
+                                        "(compiled: 1,2,4,8,16,32)", g.nb);
+    if (g.qstats) return VR_OK;  // baked for this quantile: any change drops the plane
+    vr::Params P;
+    std::memset(&P, 0, sizeof P);
+    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
+    P.sy = g.sy; P.sz = g.sz;
+    P.nb = g.nb;
+    uint64_t psy = 0, psz = 0;
+    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
+    const uint64_t plane = psz * (uint64_t)g.nz;
+    float *buf = nullptr;
+    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
+    // (the plane's padding is read with weight 0: it must hold finite floats)
+    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
+    if (e == hipSuccess)
+        e = vr::launch_bake_quant(g.vol, is_f16(), P, g.qq, g.qmode == 2, buf, psy, psz,
+                                  g.stream);
+    // synchronous, like vr_bake_stats: a later frame may run on another stream
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(g.stream);
+        (void)hipFree(buf);
+        if (e == hipErrorInvalidValue)
+            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
+                                            "slices)", g.nx, g.ny, g.nz);
+        return hip_fail(e, "vr_bake_quantile(k_bake_quant)");
+    }
+    g.qstats = buf;
+    g.qplane = plane;
+    g.qsy = psy;
+    g.qsz = psz;
+    g.volume_epoch++;
+    return VR_OK;
+}
+
+int vr_release_quantile(void) {
+    release_quantile();
+    return VR_OK;
+}
+
+int vr_quantile_info(const float **d_plane, uint64_t *plane_floats) {
+    if (d_plane) *d_plane = g.qstats;
+    if (plane_floats) *plane_floats = g.qplane;
     return VR_OK;
 }
 

@@ -597,6 +597,54 @@ __device__ __forceinline__ float lin_stat(const float (&p)[B], const float *w) {
     return acc;
 }
 
+// The quantile query (method 11): the value on the
+// normalised axis [0, 1] where the record's CDF reaches q, bin i covering
+// [i / B, (i + 1) / B) with its mass spread uniformly.  All float, in this order
+// (numpy float32 restates it bit for bit): the prefix sums c_i = c_{i-1} + p_i,
+// T = c_{B-1}, tau = q * T, k = the smallest i with c_i >= tau and p_i > 0 (B - 1
+// if none), frac = (tau - c_{k-1}) / p_k clamped to [0, 1] (an IEEE division,
+// subnormal quotients kept; NaN -> 0), Q = (k + frac) / B, 0 for T <= 0.  No
+// normalisation of the record.  The search is a chain of selects from the last
+// bin down, so the smallest i wins and the record is never indexed dynamically.
+template <int B>
+__device__ __forceinline__ float quant_at(const float (&p)[B], const float (&c)[B], float q) {
+    const float T = c[B - 1];
+    const float tau = q * T;
+    float kf = (float)(B - 1), cp = B > 1 ? c[B > 1 ? B - 2 : 0] : 0.0f, pk = p[B - 1];
+#pragma unroll
+    for (int i = B - 1; i >= 0; i--) {
+        const bool here = (c[i] >= tau) && (p[i] > 0.0f);
+        kf = here ? (float)i : kf;
+        cp = here ? (i > 0 ? c[i > 0 ? i - 1 : 0] : 0.0f) : cp;
+        pk = here ? p[i] : pk;
+    }
+    const float num = tau - cp;
+    float frac = pk > 0.0f ? num / pk : 0.0f;
+    frac = frac > 0.0f ? (frac > 1.0f ? 1.0f : frac) : 0.0f;
+    const float Q = (kf + frac) * (1.0f / (float)B);  // B a power of two: an exact scale
+    return T > 0.0f ? Q : 0.0f;
+}
+
+// SPREAD: Q(q_hi) - Q(q_lo), both from the same prefix sums; else Q(q_lo)
+template <int B, bool SPREAD>
+__device__ __forceinline__ float quant_stat(const float (&p)[B], float q_lo, float q_hi) {
+    static_assert((B & (B - 1)) == 0, "1 / B must be exact");
+    float c[B];
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < B; i++) {
+        acc = acc + p[i];
+        c[i] = acc;
+    }
+    const float lo = quant_at<B>(p, c, q_lo);
+    if constexpr (SPREAD) {
+        const float hi = quant_at<B>(p, c, q_hi);
+        return hi - lo;
+    } else {
+        return lo;
+    }
+}
+
 // record_stat with the entropy's log table in LDS (tab: copy_logtab)
 template <int B, int M>
 __device__ __forceinline__ float record_stat_p(const float (&p)[B], float enorm, const LogEnt *tab) {

@@ -156,6 +156,20 @@ hipError_t launch_march_lin(const void *vol, bool half, const Params &P, const B
 // the 16 x 2 x 1 bricks of pitches psy / psz (launch_bake_raw's layout and limits)
 hipError_t launch_bake_lin(const void *vol, bool half, const Params &P, const BinWeights &w,
                            float *out, uint64_t psy, uint64_t psz, hipStream_t s);
+// ---- quantile query (method 11, vr_quantile.hip) ----
+// the quantiles of a launch: a kernel argument of their own after Params
+// (a single quantile: q_lo == q_hi, the kernels of spread = false read q_lo)
+struct QuantArgs {
+    float q_lo, q_hi;
+};
+// k_march_quant: the march of launch_march_lin with Q(q_lo), or with
+// Q(q_hi) - Q(q_lo) when spread, per corner; same bin counts and errors
+hipError_t launch_march_quant(const void *vol, bool half, const Params &P, const QuantArgs &q,
+                              bool spread, uint32_t nslots, hipStream_t s);
+// k_bake_quant: the same statistic of every voxel into one float plane
+// (launch_bake_lin's layout and limits)
+hipError_t launch_bake_quant(const void *vol, bool half, const Params &P, const QuantArgs &q,
+                             bool spread, float *out, uint64_t psy, uint64_t psz, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,

@@ -15,192 +15,24 @@
 //                    in the 16 x 2 x 1 bricks of vr_bake_stats; a frame from the
 //                    plane is bit-identical (the same eight floats enter the
 //                    same filter).
-#include "vr_device.h"
-#include "vr_half.h"
-#include "vr_internal.h"
-#include "vr_march.h"
-
-#include <type_traits>
+#include "vr_query.h"
 
 namespace vr {
 
-// a corner's record as it is kept between gather and decode: floats, or the
-// halves still packed two per register (widened at decode)
-template <typename T, int B>
-struct LinRec {
-    float p[B];
-};
-template <int B>
-struct LinRec<_Float16, B> {
-    RecH<B> h;
-};
-
-template <typename T, int B>
-__device__ __forceinline__ void load_lin(const T *__restrict__ vol, uint64_t vidx,
-                                         LinRec<T, B> &r) {
-    if constexpr (std::is_same<T, float>::value) load_rec<B>(vol, vidx, r.p);
-    else load_rec_h<B>(vol, vidx, r.h);
-}
-
-template <typename T, int B>
-__device__ __forceinline__ float stat_lin(const LinRec<T, B> &r, const BinWeights &W) {
-    if constexpr (std::is_same<T, float>::value) {
-        return lin_stat<B>(r.p, W.w);
-    } else {
-        float p[B];
-        widen_rec<B>(r.h, p);
-        return lin_stat<B>(p, W.w);
-    }
-}
-
-// corners J0 .. J0 + N - 1 of footprint f (corner j: x = j & 1, y = j & 2,
-// z = j & 4, the order of gather8), records in x rows.  The footprint's indices
-// are clamped to the volume, so every corner is a valid record.
-template <typename T, int B, int N>
-__device__ __forceinline__ void gather_lin(const T *__restrict__ vol, const Params &P,
-                                           const Foot &f, int j0, LinRec<T, B> (&rec)[N]) {
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const int c = j0 + j;
-        const uint64_t z = (c & 4) ? (uint64_t)f.z1 : (uint64_t)f.z0;
-        const uint64_t y = (c & 2) ? (uint64_t)f.y1 : (uint64_t)f.y0;
-        const uint64_t x = (c & 1) ? (uint64_t)f.x1 : (uint64_t)f.x0;
-        load_lin<T, B>(vol, z * P.sz + y * P.sy + x, rec[j]);
-    }
-}
-
-// Corners gathered per batch.  8: two whole sets of 8 corners, the loop unrolled
-// by two so they swap roles without copies (march_pipe_tile); it fits while two
-// sets stay within 128 registers: fp32 B <= 8, f16 B <= 16.  Wider records go in
-// batches of 4 or 2 corners (64 registers a batch, two batches live), as
-// march_h32_tile and march_wide_tile do, so no instance needs scratch.
-template <typename T, int B>
-constexpr int lin_batch() {
-    constexpr int regs = std::is_same<T, float>::value ? B : (B + 1) / 2;  // per corner
-    return regs <= 8 ? 8 : regs <= 16 ? 4 : 2;
-}
-
-// the ray of thread tid of a tile; false: outside the rendered rectangle or a
-// miss (written), nothing to march
-struct LinRay {
-    Ray r;
-    uint64_t o;
-};
-__device__ __forceinline__ bool lin_ray(const Params &P, uint32_t slot, uint32_t tile,
-                                        uint32_t tid, LinRay &q) {
-    uint32_t lx, ly;
-    lane_pixel(P, tid, lx, ly);
-    const uint32_t x = (tile % P.tiles_x) * kTileW + lx;
-    const uint32_t y = (tile / P.tiles_x) * kTileH + ly;
-    if (x >= P.CW || y >= P.CH) return false;  // no cross-lane work in this kernel
-    q.o = P.tile_list ? (uint64_t)slot * 256u + ly * kTileW + lx : (uint64_t)y * P.W + x;
-    if (!make_ray(P, x, y, q.r)) {
-        write_miss(P, q.o);
-        return false;
-    }
-    return true;
-}
-
-// two sets of 8 corners: march_pipe_tile / march_h_tile with lin_stat per corner
-template <typename T, int B>
-__device__ __forceinline__ int march_lin_tile(const T *__restrict__ vol, const Params &P,
-                                              const BinWeights &W, uint32_t slot, uint32_t tile,
-                                              uint32_t tid) {
-    LinRay q;
-    if (!lin_ray(P, slot, tile, tid, q)) return -1;
-    const Ray &r = q.r;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
-    float t = r.tnear;
-    float px = r.ox + r.dx * r.tnear, py = r.oy + r.dy * r.tnear, pz = r.oz + r.dz * r.tnear;
-    const float stx = r.dx * kTStep, sty = r.dy * kTStep, stz = r.dz * kTStep;
-    int n = 0;
-    bool alive = true;
-    Foot fa = footprint(P, px, py, pz), fb;
-    LinRec<T, B> ra[8], rb[8];
-    gather_lin<T, B, 8>(vol, P, fa, 0, ra);
-    // one step: decode (fc, rc) while the gathers of the next step go to (fn, rn);
-    // the next step is gathered unconditionally (clamped indices: always valid)
-    auto step = [&](int i, const Foot &fc, const LinRec<T, B> (&rc)[8], Foot &fn,
-                    LinRec<T, B> (&rn)[8]) {
-        const float tn = t + kTStep;                               // K:701
-        const bool cont = !(tn > r.tfar) && (i + 1 < kMaxSteps);  // K:703, K:381
-        const float nx = px + stx, ny = py + sty, nz = pz + stz;   // K:706
-        fn = footprint(P, nx, ny, nz);
-        gather_lin<T, B, 8>(vol, P, fn, 0, rn);
-        float s[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) s[j] = stat_lin<T, B>(rc[j], W);
-        const float sample = blend8(s, fc);
-        n = i + 1;
-        if (composite(P, sample, sx, sy, sz, sw) || !cont) {
-            alive = false;
+// the statistic of the shared loops (vr_query.h): lin_stat against the launch's weights
+struct LinStat {
+    const BinWeights &W;
+    template <typename T, int B>
+    __device__ __forceinline__ float operator()(const LinRec<T, B> &r) const {
+        if constexpr (std::is_same<T, float>::value) {
+            return lin_stat<B>(r.p, W.w);
         } else {
-            t = tn;
-            px = nx;
-            py = ny;
-            pz = nz;
+            float p[B];
+            widen_rec<B>(r.h, p);
+            return lin_stat<B>(p, W.w);
         }
-    };
-    for (int i = 0; i < kMaxSteps; i += 2) {
-        step(i, fa, ra, fb, rb);
-        if (!alive) break;
-        step(i + 1, fb, rb, fa, ra);
-        if (!alive) break;
     }
-    write_pixel(P, q.o, n, sx * P.brightness, sy * P.brightness, sz * P.brightness,
-                sw * P.brightness);
-    return n;
-}
-
-// wide records: a step's corners in 8 / N batches of N, two batches live (ra, rb).
-// While one batch decodes the next is in flight -- after a step's last batch, the
-// first batch of the next step's footprint, gathered unconditionally
-// (march_h32_tile's order for N = 4).
-template <typename T, int B, int N>
-__device__ __forceinline__ int march_lin_batched(const T *__restrict__ vol, const Params &P,
-                                                 const BinWeights &W, uint32_t slot,
-                                                 uint32_t tile, uint32_t tid) {
-    static_assert(N == 2 || N == 4, "an even number of batches per step");
-    LinRay q;
-    if (!lin_ray(P, slot, tile, tid, q)) return -1;
-    const Ray &r = q.r;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
-    float t = r.tnear;
-    float px = r.ox + r.dx * r.tnear, py = r.oy + r.dy * r.tnear, pz = r.oz + r.dz * r.tnear;
-    const float stx = r.dx * kTStep, sty = r.dy * kTStep, stz = r.dz * kTStep;
-    int n = 0;
-    Foot fc = footprint(P, px, py, pz);
-    LinRec<T, B> ra[N], rb[N];
-    gather_lin<T, B, N>(vol, P, fc, 0, ra);
-    for (int i = 0; i < kMaxSteps; i++) {
-        const float tn = t + kTStep;                               // K:701
-        const bool cont = !(tn > r.tfar) && (i + 1 < kMaxSteps);  // K:703, K:381
-        const float nx = px + stx, ny = py + sty, nz = pz + stz;   // K:706
-        const Foot fn = footprint(P, nx, ny, nz);
-        float s[8];
-#pragma unroll
-        for (int k = 0; k < 8; k += 2 * N) {
-            gather_lin<T, B, N>(vol, P, fc, k + N, rb);
-#pragma unroll
-            for (int j = 0; j < N; j++) s[k + j] = stat_lin<T, B>(ra[j], W);
-            if (k + 2 * N < 8) gather_lin<T, B, N>(vol, P, fc, k + 2 * N, ra);
-            else gather_lin<T, B, N>(vol, P, fn, 0, ra);
-#pragma unroll
-            for (int j = 0; j < N; j++) s[k + N + j] = stat_lin<T, B>(rb[j], W);
-        }
-        const float sample = blend8(s, fc);
-        n = i + 1;
-        if (composite(P, sample, sx, sy, sz, sw) || !cont) break;
-        t = tn;
-        px = nx;
-        py = ny;
-        pz = nz;
-        fc = fn;
-    }
-    write_pixel(P, q.o, n, sx * P.brightness, sy * P.brightness, sz * P.brightness,
-                sw * P.brightness);
-    return n;
-}
+};
 
 // Waves per SIMD the register allocation may assume: the caps of the f16 march
 // (VR_PIPEH_MAXWAVES, vr_half.hip) -- 3 at B = 8, 2 for the wide records, none
@@ -210,29 +42,14 @@ __device__ __forceinline__ int march_lin_batched(const T *__restrict__ vol, cons
 #endif
 template <typename T, int B>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, VR_LIN_MAXWAVES(B)))) void k_march_lin(const T *__restrict__ vol, Params P, BinWeights W) {
-    const uint32_t slot = launch_slot(P);
-    const uint32_t tile = tile_of(P, slot);
-    if (tile == kPad) return;
-    constexpr int N = lin_batch<T, B>();
-    int n;
-    if constexpr (N == 8) n = march_lin_tile<T, B>(vol, P, W, slot, tile, threadIdx.x);
-    else n = march_lin_batched<T, B, N>(vol, P, W, slot, tile, threadIdx.x);
-    if (P.tile_cost) record_tile_cost(P, tile, n);  // all lanes have reconverged here
+    march_lin_kernel<T, B, lin_batch<T, B>()>(vol, P, LinStat{W});
 }
 
-// One thread per voxel of an x row (grid: x blocks of 256, y rows, z slices), as
-// k_bake_raw: each record read once, coalesced, its statistic written through
-// put_plane (home position and, for x = 15 k, the apron of brick k - 1).
 template <typename T, int B>
 __global__ __launch_bounds__(256) void k_bake_lin(const T *__restrict__ vol, Params P,
                                                   BinWeights W, float *__restrict__ out,
                                                   uint64_t psy, uint64_t psz) {
-    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
-    if (x >= (uint32_t)P.nx) return;
-    const uint64_t off = (uint64_t)blockIdx.z * P.sz + (uint64_t)blockIdx.y * P.sy + x;
-    LinRec<T, B> r;
-    load_lin<T, B>(vol, off, r);
-    put_plane(out, x, blockIdx.y, blockIdx.z, psy, psz, stat_lin<T, B>(r, W));
+    bake_lin_kernel<T, B>(vol, P, LinStat{W}, out, psy, psz);
 }
 
 template <typename T>
@@ -263,9 +80,9 @@ hipError_t launch_march_lin(const void *vol, bool half, const Params &P, const B
 template <typename T>
 static hipError_t bake_lin_t(const T *vol, const Params &P, const BinWeights &W, float *out,
                              uint64_t psy, uint64_t psz, hipStream_t s) {
-    if (P.nx <= 0 || P.ny <= 0 || P.nz <= 0 || P.ny > 65535 || P.nz > 65535)
-        return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)(P.nx + 255) / 256u, (uint32_t)P.ny, (uint32_t)P.nz), block(256);
+    dim3 grid;
+    const dim3 block(256);
+    if (!bake_lin_grid(P, grid)) return hipErrorInvalidValue;
     switch (P.nb) {
     case 1: hipLaunchKernelGGL((k_bake_lin<T, 1>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
     case 2: hipLaunchKernelGGL((k_bake_lin<T, 2>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
