@@ -483,8 +483,9 @@ int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int 
  * VR_ERR_STATE without one.
  *
  * Every call on the selected slot honours its element type: vr_render_gmm
- * (whole frames and slab launches; queryMethod 1 and 2, anything else
- * VR_ERR_UNSUPPORTED as for fp32), vr_gmm_count_footprint(_slab), vr_gmm_info,
+ * (whole frames and slab launches; queryMethod 1 and 2, and 10 once a range is
+ * set -- vr_set_gmm_range below --, anything else VR_ERR_UNSUPPORTED as for
+ * fp32), vr_gmm_count_footprint(_slab), vr_gmm_info,
  * vr_free_gmm, freeCudaBuffers.  The alive list of a slab chain is the same
  * 36-byte entry, so slabs of either type may hand rays to each other. */
 int vr_init_gmm_f16(const void *wm, const void *sigma, vr_extent dims, int ncomp, int z_base,
@@ -582,8 +583,8 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
  * planes), a plane's length in floats and the number of distinct slices baked;
  * any argument may be NULL.
  *
- * vr_render_gmm_baked: a whole frame of queryMethod 1 or 2 (others:
- * VR_ERR_UNSUPPORTED) from the planes; VR_ERR_STATE unless all Z slices are
+ * vr_render_gmm_baked: a whole frame of queryMethod 1 or 2 (10: from the range
+ * plane of vr_bake_gmm_range below; others: VR_ERR_UNSUPPORTED) from the planes; VR_ERR_STATE unless all Z slices are
  * baked.  No GMM records need be resident, and vr_render_gmm is unaffected by
  * the planes: it keeps decoding the records per step.  desc: everything
  * vr_render takes -- d_output_f, d_steps and d_tile_list / n_tiles (padding
@@ -699,6 +700,82 @@ int vr_quantile(float *q_lo, float *q_hi, int *spread);
 int vr_bake_quantile(void);
 int vr_release_quantile(void);
 int vr_quantile_info(const float **d_plane, uint64_t *plane_floats);
+
+/* The range probability of GMM volumes: queryMethod 10
+ * (VR_QUERY_WEIGHTED) on a GMM volume samples the mixture's mass in [lo, hi),
+ *   s = sum_k w_k (Phi((hi - mu_k) / sigma_k) - Phi((lo - mu_k) / sigma_k)),
+ * the meaning vr_set_query_range gives the method on histogram volumes; lo = -inf
+ * is the CDF at hi, hi = +inf the exceedance of lo.  lo and hi are on the axis mu
+ * lives on and nothing is clamped to [0, 1].
+ * Arithmetic: float throughout, f16 records widened first (exact), every
+ * multiply and add separate (no fma anywhere), so numpy float32 restates it bit
+ * for bit.  Per component k:
+ *   r   = 1.0f / sigma_k                         (IEEE division)
+ *   ok  = sigma_k > 0 and r is finite
+ *   eh  = ok ? E((hi - mu_k) * r) : (mu_k < hi ? 0.5f : -0.5f)
+ *   el  = ok ? E((lo - mu_k) * r) : (mu_k < lo ? 0.5f : -0.5f)
+ *   t_k = w_k * (eh - el)
+ * so a component with sigma = 0 (or with a reciprocal that overflows) is a Dirac
+ * that counts exactly when lo <= mu < hi.  Lane s of the voxel's L = K / 4 lanes
+ * forms p = t_4s; p = p + t_4s+1; p = p + t_4s+2; p = p + t_4s+3, and the lanes'
+ * p are summed by the pairwise tree of vr_gmm.hip (T(p)).
+ * Records with NaN or infinite fields get whatever these lines give.
+ * E(z) = Phi(z) - 1/2 is odd and read from a table of cubic segments:
+ *   a = fmin(|z|, ZMAX)                          (a NaN z takes ZMAX)
+ *   i = (int)(a * (1 / h));  t = a - (float)i * h    (h a power of two: both exact)
+ *   e = c0[i] + t * (c1[i] + t * (c2[i] + t * c3[i]))
+ *   E = copysign(e, z)
+ * with h = 1/16, ZMAX = 5 and 80 segments, plus the row i = 80 = (0.5, 0, 0, 0)
+ * that a = ZMAX reads: E(0) = 0 and E(+-inf) = +-0.5 exactly.  |E - E_true| <=
+ * 2.9e-7 < 2^-18 for every z (largest at the clamp), so with sum w = 1 a voxel's
+ * probability is within 2^-16 of the true value.  The table is not strictly
+ * monotone: at some segment joints it dips by 1 ulp (3e-8), so a very narrow
+ * range can give about -3e-8; the transfer function clamps.
+ * vr_gmm_phi_table: the constants the kernels use -- *c: four arrays c0 .. c3 of
+ * *nseg + 1 floats each, one after the other (host memory, never freed), *h,
+ * *zmax; any argument may be NULL.  No device call.
+ *
+ * vr_set_gmm_range: the bounds.  NaN or lo > hi: VR_ERR_ARG, the state stays as
+ * it was; +-inf is allowed.  Host state only: no device call, so it works
+ * without a GPU and before any volume is resident.  vr_clear_gmm_range: none
+ * set.  Both drop the baked range plane.  vr_gmm_range: the bounds (either
+ * argument may be NULL); VR_ERR_STATE if none are set.
+ *
+ * vr_render_gmm with queryMethod 10: VR_ERR_STATE without a range; fp32 and f16
+ * volumes, both slots, whole frames and slabs (the alive list is the one of
+ * methods 1/2).  vr_last_kernel: "k_march_gmm_range<B=K,M=10>" /
+ * "k_march_gmm_range_h<...>".  vr_gmm_count_footprint(_slab) with queryMethod
+ * 10: VR_ERR_UNSUPPORTED.
+ *
+ * vr_bake_gmm_range: the statistic of the selected slot's resident slices,
+ * decoded once per voxel with the same arithmetic, into one whole-volume float
+ * plane of its own in the layout and pitches given at vr_bake_gmm_stats, with
+ * its own per-slice flags: the first call allocates it (zeroed), later calls
+ * must come from a volume of the same dims, and a volume that never fits is
+ * baked slab by slab.  Queued on the library stream.  VR_ERR_STATE: no GMM
+ * volume in the selected slot, no range set, or other dims; VR_ERR_UNSUPPORTED
+ * and VR_ERR_HIP as for vr_bake_gmm_stats.  The plane is independent of the
+ * mean / variance planes: either may be resident without the other and neither
+ * call touches the other's plane.  It survives vr_init_gmm*, vr_synthesize_gmm*,
+ * vr_convert_gmm_f16, vr_free_gmm and vr_gmm_select, and is dropped by
+ * vr_set_gmm_range, vr_clear_gmm_range, vr_release_gmm_range and
+ * freeCudaBuffers.  As for vr_bake_gmm_stats: A CALLER WHO CHANGES THE VOLUME'S
+ * RECORDS (new data of the same dims, or records modified in place) MUST CALL
+ * vr_release_gmm_range BEFORE BAKING AGAIN, or frames mix old and new slices.
+ * vr_gmm_range_info: as vr_gmm_stats_info, for the one range plane.
+ *
+ * vr_render_gmm_baked with queryMethod 10: a whole frame from the range plane by
+ * the plane march ("<B=1,M=0>"), bit-identical to the per-step frame; tile
+ * lists, d_output_f and d_steps as for methods 1/2.  VR_ERR_STATE: no range
+ * plane, or not all slices baked. */
+int vr_set_gmm_range(float lo, float hi);
+int vr_clear_gmm_range(void);
+int vr_gmm_range(float *lo, float *hi);
+int vr_gmm_phi_table(const float **c, int *nseg, float *h, float *zmax);
+int vr_bake_gmm_range(void);
+int vr_release_gmm_range(void);
+int vr_gmm_range_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
+                      int *slices_baked);
 
 /* library version string */
 const char *vr_version(void);

@@ -110,6 +110,8 @@ EXPORTS = [
     "vr_release_weighted", "vr_weighted_info",
     "vr_set_quantile", "vr_set_quantile_spread", "vr_clear_quantile", "vr_quantile",
     "vr_bake_quantile", "vr_release_quantile", "vr_quantile_info",
+    "vr_set_gmm_range", "vr_clear_gmm_range", "vr_gmm_range", "vr_gmm_phi_table",
+    "vr_bake_gmm_range", "vr_release_gmm_range", "vr_gmm_range_info",
 ]
 
 _lib = None
@@ -274,6 +276,20 @@ def load() -> ctypes.CDLL:
     L.vr_release_quantile.restype = i32
     L.vr_quantile_info.argtypes = [vp] * 2
     L.vr_quantile_info.restype = i32
+    L.vr_set_gmm_range.argtypes = [f32, f32]
+    L.vr_set_gmm_range.restype = i32
+    L.vr_clear_gmm_range.argtypes = []
+    L.vr_clear_gmm_range.restype = i32
+    L.vr_gmm_range.argtypes = [vp] * 2
+    L.vr_gmm_range.restype = i32
+    L.vr_gmm_phi_table.argtypes = [vp] * 4
+    L.vr_gmm_phi_table.restype = i32
+    L.vr_bake_gmm_range.argtypes = []
+    L.vr_bake_gmm_range.restype = i32
+    L.vr_release_gmm_range.argtypes = []
+    L.vr_release_gmm_range.restype = i32
+    L.vr_gmm_range_info.argtypes = [vp] * 4
+    L.vr_gmm_range_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

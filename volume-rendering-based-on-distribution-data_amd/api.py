@@ -732,6 +732,66 @@ def quantile_info():
     return p.value, n.value
 
 
+# ------------------- range probability of GMM volumes (method 10)
+
+def set_gmm_range(lo: float, hi: float) -> None:
+    """Set query method 10 on GMM volumes to P(lo <= v < hi) of a voxel's mixture;
+    lo = -inf gives the CDF at hi, hi = +inf the exceedance of lo.  Host state
+    only; the baked range plane is dropped."""
+    check(_lib.load().vr_set_gmm_range(float(lo), float(hi)))
+
+
+def clear_gmm_range() -> None:
+    """No range set; the baked range plane is dropped."""
+    check(_lib.load().vr_clear_gmm_range())
+
+
+def gmm_range():
+    """(lo, hi) as set (float32 values); VRError (VR_ERR_STATE) if none is."""
+    lo, hi = ctypes.c_float(), ctypes.c_float()
+    check(_lib.load().vr_gmm_range(ctypes.addressof(lo), ctypes.addressof(hi)))
+    return lo.value, hi.value
+
+
+def gmm_phi_table():
+    """(c (4, nseg + 1) float32, nseg, h, zmax): the table of E = Phi - 1/2 the
+    range-probability kernels read (vr_gmm_phi_table), c[j][i] the coefficient
+    of t^j in segment i; a read-only copy."""
+    p, n = ctypes.c_void_p(), ctypes.c_int()
+    h, zmax = ctypes.c_float(), ctypes.c_float()
+    check(_lib.load().vr_gmm_phi_table(ctypes.addressof(p), ctypes.addressof(n),
+                                       ctypes.addressof(h), ctypes.addressof(zmax)))
+    rows = n.value + 1
+    c = np.ctypeslib.as_array(ctypes.cast(p.value, ctypes.POINTER(ctypes.c_float)),
+                              shape=(4, rows)).copy()
+    c.setflags(write=False)
+    return c, n.value, h.value, zmax.value
+
+
+def bake_gmm_range() -> None:
+    """Decode the range probability of the selected slot's resident slices once per
+    voxel into the library's whole-volume range plane (vr_bake_gmm_range), queued
+    on the library stream.  A plane of its own beside the bake_gmm_stats planes,
+    baked slab by slab like them; render_gmm_baked with query method 10 reads it.
+    Records that change need release_gmm_range() before they are baked again."""
+    check(_lib.load().vr_bake_gmm_range())
+
+
+def release_gmm_range() -> None:
+    """Free the baked range plane (the range stays set)."""
+    check(_lib.load().vr_release_gmm_range())
+
+
+def gmm_range_info():
+    """((X, Y, Z), plane_ptr, plane_floats, slices_baked) of the baked range plane;
+    plane_ptr None = no plane."""
+    e = Extent()
+    p, n, k = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_int()
+    check(_lib.load().vr_gmm_range_info(ctypes.byref(e), ctypes.byref(p), ctypes.byref(n),
+                                        ctypes.byref(k)))
+    return (e.width, e.height, e.depth), p.value, n.value, k.value
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -751,5 +811,7 @@ __all__ = [
     "bake_weighted", "release_weighted", "weighted_info",
     "QUERY_QUANTILE", "set_quantile", "set_quantile_spread", "quantile", "bake_quantile",
     "release_quantile", "quantile_info",
+    "set_gmm_range", "clear_gmm_range", "gmm_range", "gmm_phi_table", "bake_gmm_range",
+    "release_gmm_range", "gmm_range_info",
     "VRError", "PAD",
 ]

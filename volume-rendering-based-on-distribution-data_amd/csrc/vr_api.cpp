@@ -16,6 +16,7 @@
 
 #include "../../include/vr.h"
 #include "vr_internal.h"
+#include "vr_phitab.h"
 
 namespace {
 
@@ -83,6 +84,12 @@ struct State {
         std::vector<unsigned char> slice;
         int nbaked = 0;
     } gstats;
+    // range probability of GMM volumes (method 10): the
+    // bounds (host state) and the plane vr_bake_gmm_range made of them -- one
+    // plane in gstats' layout, with slice flags of its own, independent of gstats
+    vr::GmmRange grq = {};
+    bool grq_set = false;
+    GmmStats grange;
     // baked statistics (basicDataProcessing / vr_bake_stats, vr_stats.hip):
     // four planes of stats_plane floats for the raw volume (methods 1/2/3 and
     // method 7's corner mean) and
@@ -1925,14 +1932,17 @@ void release_all_gmm() {
     g.gmm_slot = 0;
 }
 
-// the baked GMM planes (vr_release_gmm_stats, freeCudaBuffers)
-void release_gmm_stats() {
-    if (g.gstats.buf) {
-        (void)hipFree(g.gstats.buf);
+// baked GMM planes: the mean / variance pair (vr_release_gmm_stats) or the range
+// plane (vr_release_gmm_range, any change of the range); freeCudaBuffers: both
+void release_gmm_planes(State::GmmStats &b) {
+    if (b.buf) {
+        (void)hipFree(b.buf);
         g.volume_epoch++;  // a tile order learned on these planes is not reused
     }
-    g.gstats = State::GmmStats{};
+    b = State::GmmStats{};
 }
+void release_gmm_stats() { release_gmm_planes(g.gstats); }
+void release_gmm_range() { release_gmm_planes(g.grange); }
 
 int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
     if (K != 8 && K != 16 && K != 32)
@@ -1952,12 +1962,20 @@ int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
 
 // Parameters of a GMM launch: the reference's ray / transfer / composite
 // inputs from the descriptor, the resident slices, and the slab.
+// count: a footprint count (no instance of the range probability is built)
 int fill_gmm_params(const vr_render_desc *d, const vr_gmm_slab *slab, vr::Params &P,
-                    uint32_t &nblocks) {
+                    uint32_t &nblocks, bool count) {
     if (!d) return fail(VR_ERR_ARG, "null render descriptor");
     if (!g.gmm.wm) return fail(VR_ERR_STATE, "no GMM volume resident (vr_init_gmm / vr_synthesize_gmm)");
-    if (d->query_method != 1 && d->query_method != 2)
-        return fail(VR_ERR_UNSUPPORTED, "GMM volumes support queryMethod 1 (mean) and 2 (variance)");
+    if (d->query_method == VR_QUERY_WEIGHTED && !count) {
+        if (!g.grq_set)
+            return fail(VR_ERR_STATE, "queryMethod 10 on a GMM volume needs a range (vr_set_gmm_range)");
+    } else if (d->query_method != 1 && d->query_method != 2) {
+        return fail(VR_ERR_UNSUPPORTED, count
+                    ? "GMM footprint counts support queryMethod 1 (mean) and 2 (variance)"
+                    : "GMM volumes support queryMethod 1 (mean), 2 (variance) and 10 (range "
+                      "probability)");
+    }
     if (!d->d_output) return fail(VR_ERR_ARG, "d_output is null");
     if (d->width == 0 || d->height == 0) return fail(VR_ERR_ARG, "empty image");
     if ((uint64_t)d->width * d->height > 0xFFFFFFFFull) return fail(VR_ERR_ARG, "image too large");
@@ -2236,14 +2254,17 @@ int vr_free_gmm(void) {
 int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
     vr::Params P;
     uint32_t nblocks = 0;
-    int rc = fill_gmm_params(desc, slab, P, nblocks);
+    int rc = fill_gmm_params(desc, slab, P, nblocks, false);
     if (rc != VR_OK) return rc;
     // the alive-list counter starts from 0 on the stream the launch runs on
     // (a caller zeroing it on another stream raced the launch)
     hipError_t e = slab ? hipMemsetAsync(slab->d_n_rays_out, 0, sizeof(uint32_t), g.stream)
                         : hipSuccess;
     if (e == hipSuccess)
-        e = vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, false, g.stream);
+        e = desc->query_method == VR_QUERY_WEIGHTED
+                ? vr::launch_march_gmm_range(g.gmm.K, gmm_f16(), P, g.grq, nblocks, g.stream)
+                : vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, false,
+                                       g.stream);
     if (e != hipSuccess) return hip_fail(e, gmm_f16() ? "launch(k_march_gmm_h)" : "launch(k_march_gmm)");
     return VR_OK;
 }
@@ -2255,7 +2276,7 @@ int64_t vr_gmm_count_footprint(const vr_render_desc *desc) {
 int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_slab *slab) {
     vr::Params P;
     uint32_t nblocks = 0;
-    int rc = fill_gmm_params(desc, slab, P, nblocks);
+    int rc = fill_gmm_params(desc, slab, P, nblocks, true);
     if (rc != VR_OK) return rc;
     // one bit per resident voxel (gmm_vox indexes the resident slices)
     const uint64_t nvox = (uint64_t)g.gmm.nx * g.gmm.ny * (uint64_t)g.gmm.nzs;
@@ -2283,14 +2304,21 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
 // The selected slot's resident slices decoded once per voxel into the
 // whole-volume planes (k_bake_gmm, queued on the library stream).  The first
 // call allocates and zeroes the planes; if it fails, nothing has changed.
-int vr_bake_gmm_stats(void) {
+}  // extern "C"
+
+namespace {
+
+// vr_bake_gmm_stats (b = gstats, two planes) and vr_bake_gmm_range (b = grange, one)
+int bake_gmm_planes(State::GmmStats &b, bool range) {
     const State::Gmm &v = g.gmm;
+    const uint64_t nplanes = range ? 1 : 2;
+    const char *fn = range ? "vr_bake_gmm_range" : "vr_bake_gmm_stats";
     if (!v.wm) return fail(VR_ERR_STATE, "no GMM volume resident (vr_init_gmm / vr_synthesize_gmm)");
-    State::GmmStats &b = g.gstats;
+    if (range && !g.grq_set) return fail(VR_ERR_STATE, "no range set (vr_set_gmm_range)");
     if (b.buf && (b.nx != v.nx || b.ny != v.ny || b.nz != v.nz))
         return fail(VR_ERR_STATE, "the GMM planes hold a %d x %d x %d volume, the resident records "
-                    "are of %d x %d x %d: vr_release_gmm_stats first", b.nx, b.ny, b.nz, v.nx, v.ny,
-                    v.nz);
+                    "are of %d x %d x %d: %s first", b.nx, b.ny, b.nz, v.nx, v.ny, v.nz,
+                    range ? "vr_release_gmm_range" : "vr_release_gmm_stats");
     if (v.nx > 65535 || v.ny > 65535 || v.nzs > 65535)
         return fail(VR_ERR_UNSUPPORTED, "baking GMM volumes beyond 65535 voxels per axis");
     uint64_t psy = b.sy, psz = b.sz, plane = b.plane;
@@ -2298,22 +2326,25 @@ int vr_bake_gmm_stats(void) {
     if (!buf) {
         vr::plane_pitches((uint32_t)v.nx, (uint32_t)v.ny, psy, psz);
         plane = psz * (uint64_t)v.nz;
-        VR_HIP(hipMalloc(&buf, (2 * plane + 4) * sizeof(float)));
+        VR_HIP(hipMalloc(&buf, (nplanes * plane + 4) * sizeof(float)));
         // (the planes' padding is read with weight 0: it must hold finite floats)
-        const hipError_t e = hipMemsetAsync(buf, 0, (2 * plane + 4) * sizeof(float), g.stream);
+        const hipError_t e = hipMemsetAsync(buf, 0, (nplanes * plane + 4) * sizeof(float), g.stream);
         if (e != hipSuccess) {
             (void)hipFree(buf);
-            return hip_fail(e, "vr_bake_gmm_stats(hipMemsetAsync)");
+            return hip_fail(e, fn);
         }
     }
-    const hipError_t e = vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base,
-                                             v.nzs, buf, plane, psy, psz, g.stream);
+    const hipError_t e =
+        range ? vr::launch_bake_gmm_range(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
+                                          g.grq, buf, psy, psz, g.stream)
+              : vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs, buf,
+                                    plane, psy, psz, g.stream);
     if (e != hipSuccess) {
         if (!b.buf) {  // the planes this call allocated, once their memset has run
             (void)hipStreamSynchronize(g.stream);
             (void)hipFree(buf);
         }
-        return hip_fail(e, "launch(k_bake_gmm)");
+        return hip_fail(e, range ? "launch(k_bake_gmm_range)" : "launch(k_bake_gmm)");
     }
     if (!b.buf) {
         b.buf = buf;
@@ -2332,14 +2363,8 @@ int vr_bake_gmm_stats(void) {
     return VR_OK;
 }
 
-int vr_release_gmm_stats(void) {
-    release_gmm_stats();
-    return VR_OK;
-}
-
-int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_floats,
-                      int *slices_baked) {
-    const State::GmmStats &b = g.gstats;
+void gmm_planes_info(const State::GmmStats &b, vr_extent *dims, const float **d_planes,
+                     uint64_t *plane_floats, int *slices_baked) {
     if (dims) {
         dims->width = (size_t)b.nx;
         dims->height = (size_t)b.ny;
@@ -2348,24 +2373,96 @@ int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_f
     if (d_planes) *d_planes = b.buf;
     if (plane_floats) *plane_floats = b.plane;
     if (slices_baked) *slices_baked = b.nbaked;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_bake_gmm_stats(void) { return bake_gmm_planes(g.gstats, false); }
+
+// ---- range probability of GMM volumes ----
+// host state only: no HIP call (the plane a set or clear drops is freed, if any)
+int vr_set_gmm_range(float lo, float hi) {
+    if (lo != lo || hi != hi || lo > hi)
+        return fail(VR_ERR_ARG, "vr_set_gmm_range: bounds [%g, %g) (NaN or lo > hi)", (double)lo,
+                    (double)hi);
+    release_gmm_range();
+    g.grq = vr::GmmRange{lo, hi};
+    g.grq_set = true;
+    return VR_OK;
+}
+
+int vr_clear_gmm_range(void) {
+    release_gmm_range();
+    g.grq = vr::GmmRange{};
+    g.grq_set = false;
+    return VR_OK;
+}
+
+int vr_gmm_range(float *lo, float *hi) {
+    if (!g.grq_set) return fail(VR_ERR_STATE, "no range set (vr_set_gmm_range)");
+    if (lo) *lo = g.grq.lo;
+    if (hi) *hi = g.grq.hi;
+    return VR_OK;
+}
+
+int vr_gmm_phi_table(const float **c, int *nseg, float *h, float *zmax) {
+    if (c) *c = vr::gmm_phi_table_host();
+    if (nseg) *nseg = vr::kPhiSeg;
+    if (h) *h = vr::kPhiH;
+    if (zmax) *zmax = vr::kPhiZMax;
+    return VR_OK;
+}
+
+int vr_bake_gmm_range(void) { return bake_gmm_planes(g.grange, true); }
+
+int vr_release_gmm_range(void) {
+    release_gmm_range();
+    return VR_OK;
+}
+
+int vr_gmm_range_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
+                      int *slices_baked) {
+    gmm_planes_info(g.grange, dims, d_plane, plane_floats, slices_baked);
+    return VR_OK;
+}
+
+int vr_release_gmm_stats(void) {
+    release_gmm_stats();
+    return VR_OK;
+}
+
+int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_floats,
+                      int *slices_baked) {
+    gmm_planes_info(g.gstats, dims, d_planes, plane_floats, slices_baked);
     return VR_OK;
 }
 
 // A frame of method 1 / 2 from the baked GMM planes: vr_render's plane march
-// (plan_march with baked planes and no layout copies) on plane method - 1.
+// (plan_march with baked planes and no layout copies) on plane method - 1;
+// method 10: the same march on the range plane.
 int vr_render_gmm_baked(const vr_render_desc *desc) {
     if (!desc) return fail(VR_ERR_ARG, "null render descriptor");
-    const int qm = desc->query_method;
+    const bool range = desc->query_method == VR_QUERY_WEIGHTED;
+    // (the plane march is planned as method 1 for the range plane: it is one
+    // float per voxel like the mean's)
+    const int qm = range ? 1 : desc->query_method;
     if (qm != 1 && qm != 2)
-        return fail(VR_ERR_UNSUPPORTED, "GMM volumes support queryMethod 1 (mean) and 2 (variance)");
-    const State::GmmStats &b = g.gstats;
-    if (!b.buf) return fail(VR_ERR_STATE, "no baked GMM planes (vr_bake_gmm_stats first)");
+        return fail(VR_ERR_UNSUPPORTED, "baked GMM frames support queryMethod 1 (mean), 2 "
+                    "(variance) and 10 (range probability)");
+    const State::GmmStats &b = range ? g.grange : g.gstats;
+    if (!b.buf)
+        return fail(VR_ERR_STATE, range ? "no baked GMM range plane (vr_bake_gmm_range first)"
+                                        : "no baked GMM planes (vr_bake_gmm_stats first)");
     if (b.nbaked != b.nz)
         return fail(VR_ERR_STATE, "%d of the GMM planes' %d slices are baked", b.nbaked, b.nz);
     vr::Params P;
     uint32_t nslots = 0;
     const FrameVol v = {b.nx, b.ny, b.nz, 1, b.sy, b.sz};
-    int rc = fill_frame_params(desc, v, P, nslots, true);
+    vr_render_desc as_plane = *desc;  // (method 10 here is not the record volumes' query)
+    as_plane.query_method = qm;
+    int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
     vr::PlanIn in = {};
     in.m0 = desc->inv_view[0];
@@ -2515,6 +2612,7 @@ void freeCudaBuffers(void) {
     release_flex();
     release_all_gmm();
     release_gmm_stats();
+    release_gmm_range();
 }
 
 void setTextureFilterMode(bool bLinearFilter) { g.linear_filter = bLinearFilter; }

@@ -51,9 +51,16 @@
 // corner is one 16-byte load of (w, mu) and one 8-byte load of sigma.  (L = K/8,
 // two partials per lane added in-lane, measured slower at 1024^3 x 16 in every
 // scene: DESIGN.md 14.3.)
+//
+// Range probability (query method 10): the march and the
+// bake are templates over the per-corner statistic; GmmMoment<M> is the mean /
+// variance above, GmmRangeStat the mixture's mass in [lo, hi),
+//   sum_k w_k (Phi((hi - mu_k) / sigma_k) - Phi((lo - mu_k) / sigma_k)),
+// with Phi - 1/2 from the cubic table of vr_phitab.h, staged in LDS.
 #include "vr_half.h"
 #include "vr_internal.h"
 #include "vr_march.h"
+#include "vr_phitab.h"
 
 namespace vr {
 
@@ -155,6 +162,70 @@ __device__ __forceinline__ float gmm_stat(const GmmPart<T, M> &r) {
         return (q - mm) * 16.0f;
     }
 }
+
+// The per-corner statistic of a march or bake: kLoad names the planes it reads
+// (1: (w, mu) only, 2: sigma too) and stat<L>() is called by every lane of the group.
+template <int M>
+struct GmmMoment {
+    static constexpr int kLoad = M;
+    template <int L, typename T>
+    __device__ __forceinline__ float stat(const GmmPart<T, M> &r) const {
+        return gmm_stat<L, M>(r);
+    }
+};
+
+// ---- range probability ----
+// The table in device memory (staged into LDS by phi_stage) and on the host
+// (vr_gmm_phi_table): the same constants.
+__device__ const float kPhiTabDev[4][kPhiRows] = VR_PHI_TABLE;
+static const float kPhiTabHost[4][kPhiRows] = VR_PHI_TABLE;
+
+const float *gmm_phi_table_host() { return &kPhiTabHost[0][0]; }
+
+// Fills the workgroup's copy of the table; every thread of the 256 must call it,
+// before any wave leaves the kernel (it holds the kernel's only barrier).
+__device__ __forceinline__ void phi_stage(float *tab) {
+    const float *src = &kPhiTabDev[0][0];
+    for (uint32_t i = threadIdx.x; i < 4u * kPhiRows; i += 256u) tab[i] = src[i];
+    __syncthreads();
+}
+
+// E(z) = Phi(z) - 1/2: odd, a = min(|z|, ZMAX) (a NaN z takes ZMAX), segment
+// i = (int)(a / h) <= kPhiSeg, t = a - i h (both exact: h is a power of two), a
+// cubic in t with separate multiplies and adds.  The four coefficients sit in
+// four arrays, so lanes with scattered i read four dwords, not one 16-byte row.
+__device__ __forceinline__ float gmm_phi_e(const float *tab, float z) {
+    const float a = __builtin_fminf(__builtin_fabsf(z), kPhiZMax);
+    const int i = (int)(a * kPhiInvH);
+    const float t = a - (float)i * kPhiH;
+    const float e = tab[i] + t * (tab[kPhiRows + i] + t * (tab[2 * kPhiRows + i] + t * tab[3 * kPhiRows + i]));
+    return __builtin_copysignf(e, z);
+}
+
+struct GmmRangeStat {
+    static constexpr int kLoad = 2;
+    float lo, hi;
+    const float *tab;             // the workgroup's LDS copy of the table
+    // one component's mass in [lo, hi); sigma = 0 (or 1 / sigma not finite): a Dirac at mu
+    __device__ __forceinline__ float term(float w, float mu, float sd) const {
+        const float r = 1.0f / sd;
+        const bool ok = sd > 0.0f && __builtin_isfinite(r);
+        const float zh = (hi - mu) * r, zl = (lo - mu) * r;
+        const float eh = ok ? gmm_phi_e(tab, zh) : (mu < hi ? 0.5f : -0.5f);
+        const float el = ok ? gmm_phi_e(tab, zl) : (mu < lo ? 0.5f : -0.5f);
+        return w * (eh - el);
+    }
+    template <int L, typename T>
+    __device__ __forceinline__ float stat(const GmmPart<T, 2> &r) const {
+        float w[4], mu[4], sd[4];
+        r.part4(w, mu, sd);
+        float p = term(w[0], mu[0], sd[0]);
+        p = p + term(w[1], mu[1], sd[1]);
+        p = p + term(w[2], mu[2], sd[2]);
+        p = p + term(w[3], mu[3], sd[3]);
+        return group_sum<L>(p);
+    }
+};
 
 // ray state of one group (identical on its L lanes)
 struct GmmState {
@@ -286,9 +357,10 @@ __device__ __forceinline__ void gmm_emit(const Params &P, const GmmState &s, uin
     }
 }
 
-// the march of both kernels, T the stored element
-template <typename T, int K, int M, bool COUNT>
-__device__ __forceinline__ void gmm_march(const Params &P) {
+// the march of every kernel, T the stored element, S the statistic
+template <typename T, int K, typename S, bool COUNT>
+__device__ __forceinline__ void gmm_march(const Params &P, const S &st) {
+    constexpr int M = S::kLoad;
     constexpr int L = K / 4;              // lanes per ray
     constexpr uint32_t R = 64u / L;       // rays in flight per wave
     static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
@@ -340,7 +412,7 @@ __device__ __forceinline__ void gmm_march(const Params &P) {
                 gmm_gather<T, K, M>(P, f, sub, rc);
                 float sv[8];
 #pragma unroll
-                for (int j = 0; j < 8; j++) sv[j] = gmm_stat<L, M>(rc[j]);
+                for (int j = 0; j < 8; j++) sv[j] = st.template stat<L>(rc[j]);
                 s.n = s.n + 1;
                 bool end = composite(P, blend8(sv, f), s.sx, s.sy, s.sz, s.sw);  // K:698
                 if (!end) {
@@ -366,7 +438,7 @@ __device__ __forceinline__ void gmm_march(const Params &P) {
 #endif
 template <int K, int M, bool COUNT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVES, 8))) void k_march_gmm(Params P) {
-    gmm_march<float, K, M, COUNT>(P);
+    gmm_march<float, K, GmmMoment<M>, COUNT>(P, GmmMoment<M>{});
 }
 
 // Waves per SIMD the register allocation of the f16 march must reach (1: no
@@ -380,7 +452,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVE
 #endif
 template <int K, int M, bool COUNT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMMH_WAVES, VR_GMMH_MAXWAVES))) void k_march_gmm_h(Params P) {
-    gmm_march<_Float16, K, M, COUNT>(P);
+    gmm_march<_Float16, K, GmmMoment<M>, COUNT>(P, GmmMoment<M>{});
+}
+
+// The range-probability marches: the bounds after Params, the table staged before
+// gmm_march can return (padding tiles, waves past the alive list).
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVES, 8))) void k_march_gmm_range(Params P, GmmRange Q) {
+    __shared__ float tab[4 * kPhiRows];
+    phi_stage(tab);
+    gmm_march<float, K, GmmRangeStat, false>(P, GmmRangeStat{Q.lo, Q.hi, tab});
+}
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMMH_WAVES, VR_GMMH_MAXWAVES))) void k_march_gmm_range_h(Params P, GmmRange Q) {
+    __shared__ float tab[4 * kPhiRows];
+    phi_stage(tab);
+    gmm_march<_Float16, K, GmmRangeStat, false>(P, GmmRangeStat{Q.lo, Q.hi, tab});
 }
 
 template <bool HALF, int K, int M, bool COUNT>
@@ -427,6 +514,36 @@ hipError_t launch_march_gmm(int K, int method, bool half, const Params &P, uint3
     if (nblocks == 0) return hipSuccess;
     return half ? launch_gmm_t<true>(K, method, P, nblocks, count, s)
                 : launch_gmm_t<false>(K, method, P, nblocks, count, s);
+}
+
+template <bool HALF, int K>
+static void launch_gmm_range_k(const Params &P, const GmmRange &Q, uint32_t nblocks, hipStream_t s) {
+    // the VR_WG_PER_CU request leaves room for the kernel's static table
+    const size_t lds = cap_lds(P, P.wg_per_cu, 0, sizeof(float) * 4 * kPhiRows);
+    if constexpr (HALF)
+        hipLaunchKernelGGL((k_march_gmm_range_h<K>), dim3(nblocks), dim3(256), lds, s, P, Q);
+    else
+        hipLaunchKernelGGL((k_march_gmm_range<K>), dim3(nblocks), dim3(256), lds, s, P, Q);
+}
+
+template <bool HALF>
+static hipError_t launch_gmm_range_t(int K, const Params &P, const GmmRange &Q, uint32_t nblocks,
+                                     hipStream_t s) {
+    switch (K) {
+    case 8: launch_gmm_range_k<HALF, 8>(P, Q, nblocks, s); break;
+    case 16: launch_gmm_range_k<HALF, 16>(P, Q, nblocks, s); break;
+    case 32: launch_gmm_range_k<HALF, 32>(P, Q, nblocks, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    note_kernel(HALF ? "k_march_gmm_range_h" : "k_march_gmm_range", K, 10);
+    return hipGetLastError();
+}
+
+hipError_t launch_march_gmm_range(int K, bool half, const Params &P, const GmmRange &Q,
+                                  uint32_t nblocks, hipStream_t s) {
+    if (nblocks == 0) return hipSuccess;
+    return half ? launch_gmm_range_t<true>(K, P, Q, nblocks, s)
+                : launch_gmm_range_t<false>(K, P, Q, nblocks, s);
 }
 
 // ---- baked GMM statistics (vr_bake_gmm_stats) ----
@@ -483,6 +600,71 @@ __global__ __launch_bounds__(256) void k_bake_gmm(const T *__restrict__ wm,
         put_plane(out, x, y, z, psy, psz, m);
         put_plane(out + plane, x, y, z, psy, psz, v16);
     }
+}
+
+// The range probability of every resident voxel into one plane: k_bake_gmm's
+// mapping and loads, GmmRangeStat's arithmetic.  The table is staged before a
+// wave past the row's end leaves.
+template <typename T, int K>
+__global__ __launch_bounds__(256) void k_bake_gmm_range(const T *__restrict__ wm,
+                                                        const T *__restrict__ sg, uint32_t nx,
+                                                        uint32_t ny, uint32_t z_base, GmmRange Q,
+                                                        float *__restrict__ out, uint64_t psy,
+                                                        uint64_t psz) {
+    constexpr int L = K / 4;              // lanes per voxel
+    constexpr uint32_t R = 64u / L;       // voxels per wave
+    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
+    __shared__ float tab[4 * kPhiRows];
+    phi_stage(tab);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sub = lane % L;
+    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
+    if (x0 >= nx) return;                 // wave-uniform
+    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
+    const bool in = x < nx;
+    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
+    GmmPart<T, 2> r;
+    if constexpr (sizeof(T) == 4) {
+        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
+        r.wm[0] = a[0];
+        r.wm[1] = a[1];
+        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
+    } else {
+        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
+        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
+    }
+    const float p = GmmRangeStat{Q.lo, Q.hi, tab}.template stat<L>(r);
+    if (in && sub == 0) put_plane(out, x, y, z_base + zl, psy, psz, p);
+}
+
+template <typename T>
+static hipError_t launch_bake_gmm_range_t(const T *wm, const T *sg, int K, uint32_t nx, uint32_t ny,
+                                          uint32_t z_base, uint32_t nzs, const GmmRange &Q,
+                                          float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
+    const uint32_t per_wg = 4u * 64u / (uint32_t)(K / 4);  // voxels of a row per workgroup
+    const dim3 grid((nx + per_wg - 1) / per_wg, ny, nzs), block(256);
+    switch (K) {
+    case 8: hipLaunchKernelGGL((k_bake_gmm_range<T, 8>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
+    case 16: hipLaunchKernelGGL((k_bake_gmm_range<T, 16>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
+    case 32: hipLaunchKernelGGL((k_bake_gmm_range<T, 32>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_gmm_range(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                                 int z_base, int nzs, const GmmRange &Q, float *out, uint64_t psy,
+                                 uint64_t psz, hipStream_t s) {
+    if (nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 || nzs > 65535)
+        return hipErrorInvalidValue;
+    if (half)
+        return launch_bake_gmm_range_t(static_cast<const _Float16 *>(wm),
+                                       static_cast<const _Float16 *>(sg), K, (uint32_t)nx,
+                                       (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, Q, out, psy,
+                                       psz, s);
+    return launch_bake_gmm_range_t(static_cast<const float *>(wm), static_cast<const float *>(sg), K,
+                                   (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, Q,
+                                   out, psy, psz, s);
 }
 
 template <typename T>

@@ -106,6 +106,22 @@ hipError_t launch_synth_gmm(void *wm, void *sg, bool half, const SynthArgs &a, i
 hipError_t launch_bake_gmm(const void *wm, const void *sg, bool half, int K, int nx, int ny,
                            int z_base, int nzs, float *out, uint64_t plane, uint64_t psy,
                            uint64_t psz, hipStream_t s);
+// ---- range probability of GMM volumes (method 10, vr_gmm.hip) ----
+// the bounds of a launch: a kernel argument of their own after Params
+struct GmmRange {
+    float lo, hi;
+};
+// k_march_gmm_range / k_march_gmm_range_h: launch_march_gmm's march with the mass of
+// the mixture in [lo, hi) per corner; records its name for vr_last_kernel() (M=10)
+hipError_t launch_march_gmm_range(int K, bool half, const Params &P, const GmmRange &q,
+                                  uint32_t nblocks, hipStream_t s);
+// k_bake_gmm_range: the same statistic of the resident slices into one whole-volume
+// plane at out (launch_bake_gmm's bricks, pitches and limits)
+hipError_t launch_bake_gmm_range(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                                 int z_base, int nzs, const GmmRange &q, float *out, uint64_t psy,
+                                 uint64_t psz, hipStream_t s);
+// the table of Phi - 1/2 the kernels read: 4 arrays of kPhiRows floats (vr_phitab.h)
+const float *gmm_phi_table_host();
 // ---- baked statistics (basicDataProcessing, vr_stats.hip): planes of `plane`
 // floats each in 16 x 2 x 1 bricks of plane pitches psy / psz (plane_index),
 // statistic k+1 (raw) / C = k (codec)
