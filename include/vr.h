@@ -483,8 +483,9 @@ int vr_synthesize_gmm(vr_extent dims, int ncomp, uint64_t seed, int z_base, int 
  * VR_ERR_STATE without one.
  *
  * Every call on the selected slot honours its element type: vr_render_gmm
- * (whole frames and slab launches; queryMethod 1 and 2, and 10 once a range is
- * set -- vr_set_gmm_range below --, anything else VR_ERR_UNSUPPORTED as for
+ * (whole frames and slab launches; queryMethod 1 and 2, 10 once a range is
+ * set -- vr_set_gmm_range below -- and 11 once a quantile is set --
+ * vr_set_quantile --, anything else VR_ERR_UNSUPPORTED as for
  * fp32), vr_gmm_count_footprint(_slab), vr_gmm_info,
  * vr_free_gmm, freeCudaBuffers.  The alive list of a slab chain is the same
  * 36-byte entry, so slabs of either type may hand rays to each other. */
@@ -584,7 +585,8 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
  * any argument may be NULL.
  *
  * vr_render_gmm_baked: a whole frame of queryMethod 1 or 2 (10: from the range
- * plane of vr_bake_gmm_range below; others: VR_ERR_UNSUPPORTED) from the planes; VR_ERR_STATE unless all Z slices are
+ * plane of vr_bake_gmm_range below; 11: from the quantile plane of
+ * vr_bake_gmm_quantile below; others: VR_ERR_UNSUPPORTED) from the planes; VR_ERR_STATE unless all Z slices are
  * baked.  No GMM records need be resident, and vr_render_gmm is unaffected by
  * the planes: it keeps decoding the records per step.  desc: everything
  * vr_render takes -- d_output_f, d_steps and d_tile_list / n_tiles (padding
@@ -676,7 +678,8 @@ int vr_weighted_info(const float **d_plane, uint64_t *plane_floats);
  * between q_lo and q_hi.  q finite and in [0, 1], q_lo <= q_hi, else VR_ERR_ARG
  * and the state stays as it was.  Host state only: no device call, so they work
  * without a GPU and before any volume is resident.  vr_clear_quantile: none set.
- * Each of the three drops the baked quantile plane.
+ * Each of the three drops the baked quantile plane, and the quantile plane of
+ * GMM volumes (vr_bake_gmm_quantile below), which is made of the same state.
  * vr_quantile: what is set (a single quantile: *q_lo == *q_hi, *spread = 0; the
  * spread: *spread = 1); any argument may be NULL; VR_ERR_STATE if none is set.
  *
@@ -776,6 +779,73 @@ int vr_bake_gmm_range(void);
 int vr_release_gmm_range(void);
 int vr_gmm_range_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
                       int *slices_baked);
+
+/* The quantile of GMM volumes: queryMethod 11
+ * (VR_QUERY_QUANTILE) on a GMM volume samples the value at which the voxel's
+ * mixture CDF reaches q -- the median, a percentile --, or the spread
+ * Q(q_hi) - Q(q_lo) (the interquartile range).  The quantile is the state of
+ * vr_set_quantile / vr_set_quantile_spread / vr_clear_quantile / vr_quantile
+ * above; there is no setter of its own.  Q lives on the axis mu lives on and
+ * nothing is clamped to [0, 1].  A mixture's quantile has no closed form: it is
+ * a bisection of N = vr_gmm_quantile_steps() = 20 steps over the support.
+ * Arithmetic: float throughout, f16 records widened first (exact), every
+ * multiply and add separate (no fma anywhere), E and ZMAX the table of the range
+ * probability above, so numpy float32 restates it bit for bit.  Per voxel, lane
+ * s of its L = K / 4 lanes holding components 4s .. 4s + 3 and T the pairwise
+ * tree of vr_gmm.hip:
+ *   r_k  = 1.0f / sigma_k                        (IEEE division)
+ *   ok_k = sigma_k > 0 and r_k is finite         (else a Dirac at mu_k)
+ *   W    = T(p), p = w_4s; p = p + w_4s+1; p = p + w_4s+2; p = p + w_4s+3
+ *   a0   = fmin over k with w_k > 0 of (mu_k - ZMAX * sigma_k)
+ *   b0   = fmax over k with w_k > 0 of (mu_k + ZMAX * sigma_k)
+ *   C(x) = T(p), p = c_4s; p = p + c_4s+1; ..., c_k = w_k * (0.5f + e_k),
+ *          e_k = ok_k ? E((x - mu_k) * r_k) : (mu_k < x ? 0.5f : -0.5f)
+ *   tau  = q * W;  lo = a0;  hi = b0
+ *   N times: mid = (lo + hi) * 0.5f;  if C(mid) < tau then lo = mid else hi = mid
+ *   Q(q) = (some w_k > 0) ? hi : 0.0f
+ * and the spread is two searches on the same r, W, a0, b0, then one float
+ * subtraction.  All components enter W and C; only those of positive weight set
+ * the bracket.  Q(0) is the lower edge a0 of the support or a float next to it,
+ * Q(1) is at or next to b0; a Dirac at mu returns a value within
+ * (b0 - a0) 2^-N above mu; a record with no positive weight returns 0; records
+ * with NaN or infinite fields, or negative weights, get whatever these lines
+ * give (which of a0 = +0 and a0 = -0 a tie between the two yields is not fixed).
+ * The search leaves Q within (b0 - a0) 2^-N of the table CDF's crossing.
+ *
+ * vr_render_gmm with queryMethod 11: VR_ERR_STATE without a quantile set; fp32
+ * and f16 volumes, both slots, whole frames and slabs (the alive list is the one
+ * of methods 1/2).  vr_last_kernel: "k_march_gmm_quant<B=K,M=11>" /
+ * "k_march_gmm_quant_h<...>".  vr_gmm_count_footprint(_slab) with queryMethod
+ * 11: VR_ERR_UNSUPPORTED.  The per-step march repeats the search at all 8
+ * corners of every sample: frames are meant to come from the plane.
+ *
+ * vr_bake_gmm_quantile: the statistic of the selected slot's resident slices,
+ * decoded once per voxel with the same arithmetic, into one whole-volume float
+ * plane of its own in the layout and pitches given at vr_bake_gmm_stats, with
+ * its own per-slice flags: the first call allocates it (zeroed), later calls
+ * must come from a volume of the same dims, and a volume that never fits is
+ * baked slab by slab.  Queued on the library stream.  VR_ERR_STATE: no GMM
+ * volume in the selected slot, no quantile set, or other dims;
+ * VR_ERR_UNSUPPORTED and VR_ERR_HIP as for vr_bake_gmm_stats.  The plane is
+ * independent of the mean / variance planes and of the range plane: any of the
+ * three may be resident without the others and no call on one touches another.
+ * It survives vr_init_gmm*, vr_synthesize_gmm*, vr_convert_gmm_f16, vr_free_gmm
+ * and vr_gmm_select, and is dropped by vr_set_quantile, vr_set_quantile_spread,
+ * vr_clear_quantile, vr_release_gmm_quantile and freeCudaBuffers.  As for
+ * vr_bake_gmm_stats: A CALLER WHO CHANGES THE VOLUME'S RECORDS (new data of the
+ * same dims, or records modified in place) MUST CALL vr_release_gmm_quantile
+ * BEFORE BAKING AGAIN, or frames mix old and new slices.
+ * vr_gmm_quantile_info: as vr_gmm_stats_info, for the one quantile plane.
+ *
+ * vr_render_gmm_baked with queryMethod 11: a whole frame from the quantile plane
+ * by the plane march ("<B=1,M=0>"), bit-identical to the per-step frame; tile
+ * lists, d_output_f and d_steps as for methods 1/2.  VR_ERR_STATE: no quantile
+ * plane, or not all slices baked. */
+int vr_gmm_quantile_steps(void);
+int vr_bake_gmm_quantile(void);
+int vr_release_gmm_quantile(void);
+int vr_gmm_quantile_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
+                         int *slices_baked);
 
 /* library version string */
 const char *vr_version(void);

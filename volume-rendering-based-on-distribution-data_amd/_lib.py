@@ -112,6 +112,8 @@ EXPORTS = [
     "vr_bake_quantile", "vr_release_quantile", "vr_quantile_info",
     "vr_set_gmm_range", "vr_clear_gmm_range", "vr_gmm_range", "vr_gmm_phi_table",
     "vr_bake_gmm_range", "vr_release_gmm_range", "vr_gmm_range_info",
+    "vr_gmm_quantile_steps", "vr_bake_gmm_quantile", "vr_release_gmm_quantile",
+    "vr_gmm_quantile_info",
 ]
 
 _lib = None
@@ -290,6 +292,14 @@ def load() -> ctypes.CDLL:
     L.vr_release_gmm_range.restype = i32
     L.vr_gmm_range_info.argtypes = [vp] * 4
     L.vr_gmm_range_info.restype = i32
+    L.vr_gmm_quantile_steps.argtypes = []
+    L.vr_gmm_quantile_steps.restype = i32
+    L.vr_bake_gmm_quantile.argtypes = []
+    L.vr_bake_gmm_quantile.restype = i32
+    L.vr_release_gmm_quantile.argtypes = []
+    L.vr_release_gmm_quantile.restype = i32
+    L.vr_gmm_quantile_info.argtypes = [vp] * 4
+    L.vr_gmm_quantile_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

@@ -569,7 +569,9 @@ def gmm_slab(z_lo: int, z_hi: int, d_rays_out, d_n_rays_out, d_rays_in=None,
 
 
 def render_gmm(desc: RenderDesc, slab: Optional[_lib.GmmSlab] = None) -> None:
-    """Launch the GMM march: the whole frame (slab None) or one slab of a chain."""
+    """Launch the GMM march: the whole frame (slab None) or one slab of a chain.
+    Query methods 1 (mean), 2 (variance), 10 (range probability, set_gmm_range) and
+    11 (quantile, set_quantile / set_quantile_spread)."""
     L = _lib.load()
     check(L.vr_render_gmm(ctypes.byref(desc), None if slab is None else ctypes.byref(slab)))
 
@@ -611,9 +613,11 @@ def gmm_stats_info():
 
 
 def render_gmm_baked(desc: RenderDesc) -> None:
-    """A whole frame of query method 1 / 2 from the baked GMM planes (asynchronous):
-    bit-identical to render_gmm, with the plane march of render().  Takes tile
-    lists, d_output_f and d_steps like render(); every slice must be baked."""
+    """A whole frame of query method 1 / 2 from the baked GMM planes (asynchronous),
+    of method 10 from the range plane (bake_gmm_range) or of method 11 from the
+    quantile plane (bake_gmm_quantile): bit-identical to render_gmm, with the plane
+    march of render().  Takes tile lists, d_output_f and d_steps like render();
+    every slice must be baked."""
     check(_lib.load().vr_render_gmm_baked(ctypes.byref(desc)))
 
 
@@ -792,6 +796,40 @@ def gmm_range_info():
     return (e.width, e.height, e.depth), p.value, n.value, k.value
 
 
+# ------------------------- quantile of GMM volumes (method 11)
+# (the quantile itself: set_quantile / set_quantile_spread / quantile above)
+
+def gmm_quantile_steps() -> int:
+    """The bisection steps N of the GMM quantile search (vr_gmm_quantile_steps)."""
+    return int(_lib.load().vr_gmm_quantile_steps())
+
+
+def bake_gmm_quantile() -> None:
+    """Decode the quantile (or the spread) that is set of the selected slot's resident
+    slices once per voxel into the library's whole-volume quantile plane
+    (vr_bake_gmm_quantile), queued on the library stream.  A plane of its own beside
+    the bake_gmm_stats and bake_gmm_range planes, baked slab by slab like them;
+    render_gmm_baked with query method 11 reads it.  Any set_quantile /
+    set_quantile_spread drops it.  Records that change need release_gmm_quantile()
+    before they are baked again."""
+    check(_lib.load().vr_bake_gmm_quantile())
+
+
+def release_gmm_quantile() -> None:
+    """Free the baked GMM quantile plane (the quantile stays set)."""
+    check(_lib.load().vr_release_gmm_quantile())
+
+
+def gmm_quantile_info():
+    """((X, Y, Z), plane_ptr, plane_floats, slices_baked) of the baked GMM quantile
+    plane; plane_ptr None = no plane."""
+    e = Extent()
+    p, n, k = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_int()
+    check(_lib.load().vr_gmm_quantile_info(ctypes.byref(e), ctypes.byref(p), ctypes.byref(n),
+                                           ctypes.byref(k)))
+    return (e.width, e.height, e.depth), p.value, n.value, k.value
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -813,5 +851,6 @@ __all__ = [
     "release_quantile", "quantile_info",
     "set_gmm_range", "clear_gmm_range", "gmm_range", "gmm_phi_table", "bake_gmm_range",
     "release_gmm_range", "gmm_range_info",
+    "gmm_quantile_steps", "bake_gmm_quantile", "release_gmm_quantile", "gmm_quantile_info",
     "VRError", "PAD",
 ]

@@ -90,6 +90,10 @@ struct State {
     vr::GmmRange grq = {};
     bool grq_set = false;
     GmmStats grange;
+    // quantile of GMM volumes (method 11): the plane
+    // vr_bake_gmm_quantile made of the quantile state below (qq, qmode) -- a third
+    // plane set of one plane, independent of gstats and grange
+    GmmStats gquant;
     // baked statistics (basicDataProcessing / vr_bake_stats, vr_stats.hip):
     // four planes of stats_plane floats for the raw volume (methods 1/2/3 and
     // method 7's corner mean) and
@@ -1933,7 +1937,8 @@ void release_all_gmm() {
 }
 
 // baked GMM planes: the mean / variance pair (vr_release_gmm_stats) or the range
-// plane (vr_release_gmm_range, any change of the range); freeCudaBuffers: both
+// plane (vr_release_gmm_range, any change of the range) or the quantile plane
+// (vr_release_gmm_quantile, any set or clear of the quantile); freeCudaBuffers: all
 void release_gmm_planes(State::GmmStats &b) {
     if (b.buf) {
         (void)hipFree(b.buf);
@@ -1943,6 +1948,7 @@ void release_gmm_planes(State::GmmStats &b) {
 }
 void release_gmm_stats() { release_gmm_planes(g.gstats); }
 void release_gmm_range() { release_gmm_planes(g.grange); }
+void release_gmm_quantile() { release_gmm_planes(g.gquant); }
 
 int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
     if (K != 8 && K != 16 && K != 32)
@@ -1962,7 +1968,8 @@ int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
 
 // Parameters of a GMM launch: the reference's ray / transfer / composite
 // inputs from the descriptor, the resident slices, and the slab.
-// count: a footprint count (no instance of the range probability is built)
+// count: a footprint count (no instance of the range probability or the quantile
+// is built)
 int fill_gmm_params(const vr_render_desc *d, const vr_gmm_slab *slab, vr::Params &P,
                     uint32_t &nblocks, bool count) {
     if (!d) return fail(VR_ERR_ARG, "null render descriptor");
@@ -1970,11 +1977,15 @@ int fill_gmm_params(const vr_render_desc *d, const vr_gmm_slab *slab, vr::Params
     if (d->query_method == VR_QUERY_WEIGHTED && !count) {
         if (!g.grq_set)
             return fail(VR_ERR_STATE, "queryMethod 10 on a GMM volume needs a range (vr_set_gmm_range)");
+    } else if (d->query_method == VR_QUERY_QUANTILE && !count) {
+        if (g.qmode == 0)
+            return fail(VR_ERR_STATE, "queryMethod 11 on a GMM volume needs a quantile "
+                                      "(vr_set_quantile / vr_set_quantile_spread)");
     } else if (d->query_method != 1 && d->query_method != 2) {
         return fail(VR_ERR_UNSUPPORTED, count
                     ? "GMM footprint counts support queryMethod 1 (mean) and 2 (variance)"
-                    : "GMM volumes support queryMethod 1 (mean), 2 (variance) and 10 (range "
-                      "probability)");
+                    : "GMM volumes support queryMethod 1 (mean), 2 (variance), 10 (range "
+                      "probability) and 11 (quantile)");
     }
     if (!d->d_output) return fail(VR_ERR_ARG, "d_output is null");
     if (d->width == 0 || d->height == 0) return fail(VR_ERR_ARG, "empty image");
@@ -2260,11 +2271,16 @@ int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
     // (a caller zeroing it on another stream raced the launch)
     hipError_t e = slab ? hipMemsetAsync(slab->d_n_rays_out, 0, sizeof(uint32_t), g.stream)
                         : hipSuccess;
-    if (e == hipSuccess)
-        e = desc->query_method == VR_QUERY_WEIGHTED
-                ? vr::launch_march_gmm_range(g.gmm.K, gmm_f16(), P, g.grq, nblocks, g.stream)
-                : vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, false,
-                                       g.stream);
+    if (e == hipSuccess) {
+        if (desc->query_method == VR_QUERY_WEIGHTED)
+            e = vr::launch_march_gmm_range(g.gmm.K, gmm_f16(), P, g.grq, nblocks, g.stream);
+        else if (desc->query_method == VR_QUERY_QUANTILE)
+            e = vr::launch_march_gmm_quant(g.gmm.K, gmm_f16(), P, g.qq, g.qmode == 2, nblocks,
+                                           g.stream);
+        else
+            e = vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, false,
+                                     g.stream);
+    }
     if (e != hipSuccess) return hip_fail(e, gmm_f16() ? "launch(k_march_gmm_h)" : "launch(k_march_gmm)");
     return VR_OK;
 }
@@ -2308,17 +2324,23 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
 
 namespace {
 
-// vr_bake_gmm_stats (b = gstats, two planes) and vr_bake_gmm_range (b = grange, one)
-int bake_gmm_planes(State::GmmStats &b, bool range) {
+// vr_bake_gmm_stats (b = gstats, two planes), vr_bake_gmm_range (b = grange, one) and
+// vr_bake_gmm_quantile (b = gquant, one)
+enum GmmBake { kBakeStats, kBakeRange, kBakeQuantile };
+int bake_gmm_planes(State::GmmStats &b, GmmBake kind) {
     const State::Gmm &v = g.gmm;
-    const uint64_t nplanes = range ? 1 : 2;
-    const char *fn = range ? "vr_bake_gmm_range" : "vr_bake_gmm_stats";
+    const bool range = kind == kBakeRange, quant = kind == kBakeQuantile;
+    const uint64_t nplanes = kind == kBakeStats ? 2 : 1;
+    const char *fn = quant ? "vr_bake_gmm_quantile" : range ? "vr_bake_gmm_range" : "vr_bake_gmm_stats";
     if (!v.wm) return fail(VR_ERR_STATE, "no GMM volume resident (vr_init_gmm / vr_synthesize_gmm)");
     if (range && !g.grq_set) return fail(VR_ERR_STATE, "no range set (vr_set_gmm_range)");
+    if (quant && g.qmode == 0)
+        return fail(VR_ERR_STATE, "no quantile set (vr_set_quantile / vr_set_quantile_spread)");
     if (b.buf && (b.nx != v.nx || b.ny != v.ny || b.nz != v.nz))
         return fail(VR_ERR_STATE, "the GMM planes hold a %d x %d x %d volume, the resident records "
                     "are of %d x %d x %d: %s first", b.nx, b.ny, b.nz, v.nx, v.ny, v.nz,
-                    range ? "vr_release_gmm_range" : "vr_release_gmm_stats");
+                    quant ? "vr_release_gmm_quantile"
+                          : range ? "vr_release_gmm_range" : "vr_release_gmm_stats");
     if (v.nx > 65535 || v.ny > 65535 || v.nzs > 65535)
         return fail(VR_ERR_UNSUPPORTED, "baking GMM volumes beyond 65535 voxels per axis");
     uint64_t psy = b.sy, psz = b.sz, plane = b.plane;
@@ -2335,16 +2357,19 @@ int bake_gmm_planes(State::GmmStats &b, bool range) {
         }
     }
     const hipError_t e =
-        range ? vr::launch_bake_gmm_range(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
-                                          g.grq, buf, psy, psz, g.stream)
-              : vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs, buf,
-                                    plane, psy, psz, g.stream);
+        quant ? vr::launch_bake_gmm_quant(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
+                                          g.qq, g.qmode == 2, buf, psy, psz, g.stream)
+        : range ? vr::launch_bake_gmm_range(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
+                                            g.grq, buf, psy, psz, g.stream)
+                : vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs, buf,
+                                      plane, psy, psz, g.stream);
     if (e != hipSuccess) {
         if (!b.buf) {  // the planes this call allocated, once their memset has run
             (void)hipStreamSynchronize(g.stream);
             (void)hipFree(buf);
         }
-        return hip_fail(e, range ? "launch(k_bake_gmm_range)" : "launch(k_bake_gmm)");
+        return hip_fail(e, quant ? "launch(k_bake_gmm_quant)"
+                           : range ? "launch(k_bake_gmm_range)" : "launch(k_bake_gmm)");
     }
     if (!b.buf) {
         b.buf = buf;
@@ -2379,7 +2404,7 @@ void gmm_planes_info(const State::GmmStats &b, vr_extent *dims, const float **d_
 
 extern "C" {
 
-int vr_bake_gmm_stats(void) { return bake_gmm_planes(g.gstats, false); }
+int vr_bake_gmm_stats(void) { return bake_gmm_planes(g.gstats, kBakeStats); }
 
 // ---- range probability of GMM volumes ----
 // host state only: no HIP call (the plane a set or clear drops is freed, if any)
@@ -2415,7 +2440,7 @@ int vr_gmm_phi_table(const float **c, int *nseg, float *h, float *zmax) {
     return VR_OK;
 }
 
-int vr_bake_gmm_range(void) { return bake_gmm_planes(g.grange, true); }
+int vr_bake_gmm_range(void) { return bake_gmm_planes(g.grange, kBakeRange); }
 
 int vr_release_gmm_range(void) {
     release_gmm_range();
@@ -2425,6 +2450,23 @@ int vr_release_gmm_range(void) {
 int vr_gmm_range_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
                       int *slices_baked) {
     gmm_planes_info(g.grange, dims, d_plane, plane_floats, slices_baked);
+    return VR_OK;
+}
+
+// ---- quantile of GMM volumes: the quantile itself is the
+// state of vr_set_quantile / vr_set_quantile_spread / vr_clear_quantile ----
+int vr_gmm_quantile_steps(void) { return vr::kGmmQuantSteps; }
+
+int vr_bake_gmm_quantile(void) { return bake_gmm_planes(g.gquant, kBakeQuantile); }
+
+int vr_release_gmm_quantile(void) {
+    release_gmm_quantile();
+    return VR_OK;
+}
+
+int vr_gmm_quantile_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
+                         int *slices_baked) {
+    gmm_planes_info(g.gquant, dims, d_plane, plane_floats, slices_baked);
     return VR_OK;
 }
 
@@ -2441,26 +2483,28 @@ int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_f
 
 // A frame of method 1 / 2 from the baked GMM planes: vr_render's plane march
 // (plan_march with baked planes and no layout copies) on plane method - 1;
-// method 10: the same march on the range plane.
+// method 10: the same march on the range plane; method 11: on the quantile plane.
 int vr_render_gmm_baked(const vr_render_desc *desc) {
     if (!desc) return fail(VR_ERR_ARG, "null render descriptor");
     const bool range = desc->query_method == VR_QUERY_WEIGHTED;
-    // (the plane march is planned as method 1 for the range plane: it is one
-    // float per voxel like the mean's)
-    const int qm = range ? 1 : desc->query_method;
+    const bool quant = desc->query_method == VR_QUERY_QUANTILE;
+    // (the plane march is planned as method 1 for the range and quantile planes:
+    // each is one float per voxel like the mean's)
+    const int qm = range || quant ? 1 : desc->query_method;
     if (qm != 1 && qm != 2)
         return fail(VR_ERR_UNSUPPORTED, "baked GMM frames support queryMethod 1 (mean), 2 "
-                    "(variance) and 10 (range probability)");
-    const State::GmmStats &b = range ? g.grange : g.gstats;
+                    "(variance), 10 (range probability) and 11 (quantile)");
+    const State::GmmStats &b = quant ? g.gquant : range ? g.grange : g.gstats;
     if (!b.buf)
-        return fail(VR_ERR_STATE, range ? "no baked GMM range plane (vr_bake_gmm_range first)"
-                                        : "no baked GMM planes (vr_bake_gmm_stats first)");
+        return fail(VR_ERR_STATE, quant ? "no baked GMM quantile plane (vr_bake_gmm_quantile first)"
+                                  : range ? "no baked GMM range plane (vr_bake_gmm_range first)"
+                                          : "no baked GMM planes (vr_bake_gmm_stats first)");
     if (b.nbaked != b.nz)
         return fail(VR_ERR_STATE, "%d of the GMM planes' %d slices are baked", b.nbaked, b.nz);
     vr::Params P;
     uint32_t nslots = 0;
     const FrameVol v = {b.nx, b.ny, b.nz, 1, b.sy, b.sz};
-    vr_render_desc as_plane = *desc;  // (method 10 here is not the record volumes' query)
+    vr_render_desc as_plane = *desc;  // (methods 10 / 11 here are not the record volumes' queries)
     as_plane.query_method = qm;
     int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
@@ -2613,6 +2657,7 @@ void freeCudaBuffers(void) {
     release_all_gmm();
     release_gmm_stats();
     release_gmm_range();
+    release_gmm_quantile();
 }
 
 void setTextureFilterMode(bool bLinearFilter) { g.linear_filter = bLinearFilter; }
@@ -2735,6 +2780,7 @@ bool quantile_ok(float q) { return std::isfinite(q) && q >= 0.0f && q <= 1.0f; }
 int vr_set_quantile(float q) {
     if (!quantile_ok(q)) return fail(VR_ERR_ARG, "vr_set_quantile: q must be in [0, 1]");
     release_quantile();  // a plane baked for another quantile
+    release_gmm_quantile();
     g.qq = vr::QuantArgs{q, q};
     g.qmode = 1;
     return VR_OK;
@@ -2744,6 +2790,7 @@ int vr_set_quantile_spread(float q_lo, float q_hi) {
     if (!quantile_ok(q_lo) || !quantile_ok(q_hi) || q_lo > q_hi)
         return fail(VR_ERR_ARG, "vr_set_quantile_spread: 0 <= q_lo <= q_hi <= 1 required");
     release_quantile();
+    release_gmm_quantile();
     g.qq = vr::QuantArgs{q_lo, q_hi};
     g.qmode = 2;
     return VR_OK;
@@ -2751,6 +2798,7 @@ int vr_set_quantile_spread(float q_lo, float q_hi) {
 
 int vr_clear_quantile(void) {
     release_quantile();
+    release_gmm_quantile();
     g.qq = vr::QuantArgs{};
     g.qmode = 0;
     return VR_OK;

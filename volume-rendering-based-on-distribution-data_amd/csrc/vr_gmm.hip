@@ -57,6 +57,10 @@
 // variance above, GmmRangeStat the mixture's mass in [lo, hi),
 //   sum_k w_k (Phi((hi - mu_k) / sigma_k) - Phi((lo - mu_k) / sigma_k)),
 // with Phi - 1/2 from the cubic table of vr_phitab.h, staged in LDS.
+//
+// Quantile (query method 11): GmmQuantStat is the value at
+// which the mixture's CDF, built of the same table, reaches q W -- a bisection of
+// kGmmQuantSteps steps over the support [a0, b0] -- or the difference of two.
 #include "vr_half.h"
 #include "vr_internal.h"
 #include "vr_march.h"
@@ -70,6 +74,7 @@ namespace vr {
 // xGMI as one entry, so its size is the chain's hand-off cost.
 constexpr int kGmmRayWords = 9;
 constexpr uint32_t kGmmPixBits = 23;
+static_assert((uint32_t)kMaxSteps < (1u << (32 - kGmmPixBits)), "samples taken fit beside the pixel");
 struct GmmRay {
     float sx, sy, sz, sw;
     float t, px, py, pz;
@@ -224,6 +229,96 @@ struct GmmRangeStat {
         p = p + term(w[2], mu[2], sd[2]);
         p = p + term(w[3], mu[3], sd[3]);
         return group_sum<L>(p);
+    }
+};
+
+// ---- quantile ----
+// min / max over an L-lane group: group_sum's DPP pattern (order-independent)
+template <int L>
+__device__ __forceinline__ float group_min(float p) {
+    float s = __builtin_fminf(p, dppc<0xB1>(p));
+    if constexpr (L >= 4) s = __builtin_fminf(s, dppc<0x4E>(s));
+    if constexpr (L >= 8) s = __builtin_fminf(s, dppc<0x141>(s));
+    return s;
+}
+template <int L>
+__device__ __forceinline__ float group_max(float p) {
+    float s = __builtin_fmaxf(p, dppc<0xB1>(p));
+    if constexpr (L >= 4) s = __builtin_fmaxf(s, dppc<0x4E>(s));
+    if constexpr (L >= 8) s = __builtin_fmaxf(s, dppc<0x141>(s));
+    return s;
+}
+
+// Q(q): where the table CDF C(x) = sum_k w_k (1/2 + E((x - mu_k) / sigma_k)) reaches
+// q W, W the sum of the weights, by kGmmQuantSteps bisections of the support
+// [a0, b0] = [min (mu - ZMAX sigma), max (mu + ZMAX sigma)] over the components of
+// positive weight; SPREAD: Q(q_hi) - Q(q_lo).  A lane keeps its four components'
+// w, mu, 1 / sigma and Dirac flags in registers across the search; every lane of a
+// group sees the same C(mid) (group_sum is symmetric) and takes the same branch, and
+// the step count is fixed, so the wave does not diverge.
+template <bool SPREAD>
+struct GmmQuantStat {
+    static constexpr int kLoad = 2;
+    float q_lo, q_hi;
+    const float *tab;             // the workgroup's LDS copy of the table
+    template <int L>
+    __device__ __forceinline__ float search(const float (&w)[4], const float (&mu)[4],
+                                            const float (&r)[4], const bool (&ok)[4], float a0,
+                                            float b0, float tau) const {
+        float lo = a0, hi = b0;
+#pragma nounroll
+        for (int it = 0; it < kGmmQuantSteps; it++) {
+            const float mid = (lo + hi) * 0.5f;
+            float p = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                // (the table is read for a Dirac too, then discarded: a select, so the
+                // loop body has no branch; gmm_phi_e clamps any z to a row of the table)
+                const float et = gmm_phi_e(tab, (mid - mu[i]) * r[i]);
+                const float ed = mu[i] < mid ? 0.5f : -0.5f;
+                const float e = ok[i] ? et : ed;
+                const float c = w[i] * (0.5f + e);
+                p = i ? p + c : c;
+            }
+            const bool below = group_sum<L>(p) < tau;
+            lo = below ? mid : lo;
+            hi = below ? hi : mid;
+        }
+        return hi;
+    }
+    template <int L, typename T>
+    __device__ __forceinline__ float stat(const GmmPart<T, 2> &rec) const {
+        float w[4], mu[4], sd[4], r[4];
+        bool ok[4];
+        rec.part4(w, mu, sd);
+        float a0 = __builtin_inff(), b0 = -__builtin_inff(), live = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            r[i] = 1.0f / sd[i];
+            ok[i] = sd[i] > 0.0f && __builtin_isfinite(r[i]);
+            const float reach = kPhiZMax * sd[i];
+            if (w[i] > 0.0f) {
+                a0 = __builtin_fminf(a0, mu[i] - reach);
+                b0 = __builtin_fmaxf(b0, mu[i] + reach);
+                live = 1.0f;
+            }
+        }
+        a0 = group_min<L>(a0);
+        b0 = group_max<L>(b0);
+        live = group_max<L>(live);
+        float p = w[0];
+        p = p + w[1];
+        p = p + w[2];
+        p = p + w[3];
+        const float W = group_sum<L>(p);
+        float q = search<L>(w, mu, r, ok, a0, b0, q_lo * W);
+        q = live > 0.0f ? q : 0.0f;
+        if constexpr (SPREAD) {
+            float qh = search<L>(w, mu, r, ok, a0, b0, q_hi * W);
+            qh = live > 0.0f ? qh : 0.0f;
+            q = qh - q;
+        }
+        return q;
     }
 };
 
@@ -470,6 +565,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMMH_WAV
     gmm_march<_Float16, K, GmmRangeStat, false>(P, GmmRangeStat{Q.lo, Q.hi, tab});
 }
 
+// The quantile marches: the quantiles after Params (q_lo alone unless SPREAD), the
+// table staged as above.
+template <int K, bool SPREAD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMM_WAVES, 8))) void k_march_gmm_quant(Params P, QuantArgs Q) {
+    __shared__ float tab[4 * kPhiRows];
+    phi_stage(tab);
+    gmm_march<float, K, GmmQuantStat<SPREAD>, false>(P, GmmQuantStat<SPREAD>{Q.q_lo, Q.q_hi, tab});
+}
+template <int K, bool SPREAD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMMH_WAVES, VR_GMMH_MAXWAVES))) void k_march_gmm_quant_h(Params P, QuantArgs Q) {
+    __shared__ float tab[4 * kPhiRows];
+    phi_stage(tab);
+    gmm_march<_Float16, K, GmmQuantStat<SPREAD>, false>(P, GmmQuantStat<SPREAD>{Q.q_lo, Q.q_hi, tab});
+}
+
 template <bool HALF, int K, int M, bool COUNT>
 static void launch_gmm_km(const Params &P, uint32_t nblocks, hipStream_t s) {
     if constexpr (HALF)
@@ -544,6 +654,38 @@ hipError_t launch_march_gmm_range(int K, bool half, const Params &P, const GmmRa
     if (nblocks == 0) return hipSuccess;
     return half ? launch_gmm_range_t<true>(K, P, Q, nblocks, s)
                 : launch_gmm_range_t<false>(K, P, Q, nblocks, s);
+}
+
+template <bool HALF, int K, bool SPREAD>
+static void launch_gmm_quant_k(const Params &P, const QuantArgs &Q, uint32_t nblocks, hipStream_t s) {
+    const size_t lds = cap_lds(P, P.wg_per_cu, 0, sizeof(float) * 4 * kPhiRows);
+    if constexpr (HALF)
+        hipLaunchKernelGGL((k_march_gmm_quant_h<K, SPREAD>), dim3(nblocks), dim3(256), lds, s, P, Q);
+    else
+        hipLaunchKernelGGL((k_march_gmm_quant<K, SPREAD>), dim3(nblocks), dim3(256), lds, s, P, Q);
+}
+
+template <bool HALF, bool SPREAD>
+static hipError_t launch_gmm_quant_t(int K, const Params &P, const QuantArgs &Q, uint32_t nblocks,
+                                     hipStream_t s) {
+    switch (K) {
+    case 8: launch_gmm_quant_k<HALF, 8, SPREAD>(P, Q, nblocks, s); break;
+    case 16: launch_gmm_quant_k<HALF, 16, SPREAD>(P, Q, nblocks, s); break;
+    case 32: launch_gmm_quant_k<HALF, 32, SPREAD>(P, Q, nblocks, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    note_kernel(HALF ? "k_march_gmm_quant_h" : "k_march_gmm_quant", K, 11);
+    return hipGetLastError();
+}
+
+hipError_t launch_march_gmm_quant(int K, bool half, const Params &P, const QuantArgs &Q,
+                                  bool spread, uint32_t nblocks, hipStream_t s) {
+    if (nblocks == 0) return hipSuccess;
+    if (half)
+        return spread ? launch_gmm_quant_t<true, true>(K, P, Q, nblocks, s)
+                      : launch_gmm_quant_t<true, false>(K, P, Q, nblocks, s);
+    return spread ? launch_gmm_quant_t<false, true>(K, P, Q, nblocks, s)
+                  : launch_gmm_quant_t<false, false>(K, P, Q, nblocks, s);
 }
 
 // ---- baked GMM statistics (vr_bake_gmm_stats) ----
@@ -665,6 +807,80 @@ hipError_t launch_bake_gmm_range(const void *wm, const void *sg, bool half, int 
     return launch_bake_gmm_range_t(static_cast<const float *>(wm), static_cast<const float *>(sg), K,
                                    (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, Q,
                                    out, psy, psz, s);
+}
+
+// The quantile of every resident voxel into one plane: k_bake_gmm_range's mapping,
+// loads and store, GmmQuantStat's arithmetic.
+template <typename T, int K, bool SPREAD>
+__global__ __launch_bounds__(256) void k_bake_gmm_quant(const T *__restrict__ wm,
+                                                        const T *__restrict__ sg, uint32_t nx,
+                                                        uint32_t ny, uint32_t z_base, QuantArgs Q,
+                                                        float *__restrict__ out, uint64_t psy,
+                                                        uint64_t psz) {
+    constexpr int L = K / 4;              // lanes per voxel
+    constexpr uint32_t R = 64u / L;       // voxels per wave
+    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
+    __shared__ float tab[4 * kPhiRows];
+    phi_stage(tab);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sub = lane % L;
+    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
+    if (x0 >= nx) return;                 // wave-uniform
+    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
+    const bool in = x < nx;
+    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
+    GmmPart<T, 2> r;
+    if constexpr (sizeof(T) == 4) {
+        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
+        r.wm[0] = a[0];
+        r.wm[1] = a[1];
+        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
+    } else {
+        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
+        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
+    }
+    const float q = GmmQuantStat<SPREAD>{Q.q_lo, Q.q_hi, tab}.template stat<L>(r);
+    if (in && sub == 0) put_plane(out, x, y, z_base + zl, psy, psz, q);
+}
+
+template <typename T, bool SPREAD>
+static hipError_t launch_bake_gmm_quant_t(const T *wm, const T *sg, int K, uint32_t nx, uint32_t ny,
+                                          uint32_t z_base, uint32_t nzs, const QuantArgs &Q,
+                                          float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
+    const uint32_t per_wg = 4u * 64u / (uint32_t)(K / 4);  // voxels of a row per workgroup
+    const dim3 grid((nx + per_wg - 1) / per_wg, ny, nzs), block(256);
+    switch (K) {
+    case 8: hipLaunchKernelGGL((k_bake_gmm_quant<T, 8, SPREAD>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
+    case 16: hipLaunchKernelGGL((k_bake_gmm_quant<T, 16, SPREAD>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
+    case 32: hipLaunchKernelGGL((k_bake_gmm_quant<T, 32, SPREAD>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+template <bool SPREAD>
+static hipError_t launch_bake_gmm_quant_s(const void *wm, const void *sg, bool half, int K,
+                                          uint32_t nx, uint32_t ny, uint32_t z_base, uint32_t nzs,
+                                          const QuantArgs &Q, float *out, uint64_t psy, uint64_t psz,
+                                          hipStream_t s) {
+    if (half)
+        return launch_bake_gmm_quant_t<_Float16, SPREAD>(static_cast<const _Float16 *>(wm),
+                                                         static_cast<const _Float16 *>(sg), K, nx, ny,
+                                                         z_base, nzs, Q, out, psy, psz, s);
+    return launch_bake_gmm_quant_t<float, SPREAD>(static_cast<const float *>(wm),
+                                                  static_cast<const float *>(sg), K, nx, ny, z_base,
+                                                  nzs, Q, out, psy, psz, s);
+}
+
+hipError_t launch_bake_gmm_quant(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                                 int z_base, int nzs, const QuantArgs &Q, bool spread, float *out,
+                                 uint64_t psy, uint64_t psz, hipStream_t s) {
+    if (nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 || nzs > 65535)
+        return hipErrorInvalidValue;
+    return spread ? launch_bake_gmm_quant_s<true>(wm, sg, half, K, (uint32_t)nx, (uint32_t)ny,
+                                                  (uint32_t)z_base, (uint32_t)nzs, Q, out, psy, psz, s)
+                  : launch_bake_gmm_quant_s<false>(wm, sg, half, K, (uint32_t)nx, (uint32_t)ny,
+                                                   (uint32_t)z_base, (uint32_t)nzs, Q, out, psy, psz, s);
 }
 
 template <typename T>

@@ -186,6 +186,19 @@ hipError_t launch_march_quant(const void *vol, bool half, const Params &P, const
 // (launch_bake_lin's layout and limits)
 hipError_t launch_bake_quant(const void *vol, bool half, const Params &P, const QuantArgs &q,
                              bool spread, float *out, uint64_t psy, uint64_t psz, hipStream_t s);
+// ---- quantile of GMM volumes (method 11, vr_gmm.hip) ----
+// bisection steps of the search (vr_gmm_quantile_steps)
+constexpr int kGmmQuantSteps = 20;
+// k_march_gmm_quant / k_march_gmm_quant_h: launch_march_gmm's march with the value at
+// which the mixture's CDF reaches q_lo, or Q(q_hi) - Q(q_lo) when spread, per corner;
+// records its name for vr_last_kernel() (M=11)
+hipError_t launch_march_gmm_quant(int K, bool half, const Params &P, const QuantArgs &q,
+                                  bool spread, uint32_t nblocks, hipStream_t s);
+// k_bake_gmm_quant: the same statistic of the resident slices into one whole-volume
+// plane at out (launch_bake_gmm's bricks, pitches and limits)
+hipError_t launch_bake_gmm_quant(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                                 int z_base, int nzs, const QuantArgs &q, bool spread, float *out,
+                                 uint64_t psy, uint64_t psz, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
