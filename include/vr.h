@@ -704,6 +704,78 @@ int vr_bake_quantile(void);
 int vr_release_quantile(void);
 int vr_quantile_info(const float **d_plane, uint64_t *plane_floats);
 
+/* The distribution-distance query: queryMethod 12 samples
+ * how far a voxel's record p is from one target record h -- pick a material by
+ * its histogram, or by pointing at an example region, and see where else it
+ * occurs.  Three metrics, float throughout (f16 records widened first, which is
+ * exact), every operation separate (never fused), in bin order, subnormals kept,
+ * nothing normalised:
+ *   VR_DIST_L1  (0): a = 0;        for i = 0 .. B-1: d = p_i - h_i;
+ *                    a = a + |d|;                         D = a * 0.5f
+ *   VR_DIST_EMD (1): a = 0; e = 0; for i = 0 .. B-1: d = p_i - h_i; e = e + d;
+ *                    a = a + |e|;                         D = a * (1.0f / B)
+ *   VR_DIST_KS  (2): a = 0; e = 0; for i = 0 .. B-1: d = p_i - h_i; e = e + d;
+ *                    a = fmaxf(a, |e|);                   D = a
+ *   s = similarity ? 1.0f - D : D
+ * L1 is the total-variation distance of normalised records.  EMD is the
+ * Wasserstein-1 distance on the normalised value axis [0, 1] (bin spacing 1 / B,
+ * an exact scale); all B prefix differences are summed, so for unnormalised
+ * records the last term charges the difference of the totals.  KS is the largest
+ * CDF gap; fmaxf returns its other operand for a NaN.  Records with NaN or
+ * infinite fields get whatever these lines give.  numpy float32 restates all of
+ * it bit for bit.  Record volumes only (fp32 or f16, owned or adopted) with 1, 2,
+ * 4, 8, 16 or 32 bins; vr_render and render_kernel take the method like
+ * 1/2/3/10/11 (tile lists, d_output_f, d_steps, clipped coverage).  Every view
+ * marches the x rows of the records with k_march_dist (vr_last_kernel:
+ * "k_march_dist<B=..,M=12>"); no layout copy is used or made.
+ * vr_render / render_kernel with queryMethod 12: VR_ERR_STATE without a record
+ * volume, without a target, or with a target count other than the volume's bins;
+ * VR_ERR_UNSUPPORTED for records of any other bin count.  vr_count_footprint and
+ * vr_footprint_bytes: VR_ERR_UNSUPPORTED.  vr_render_gmm and vr_render_gmm_baked
+ * with queryMethod 12: VR_ERR_UNSUPPORTED.
+ *
+ * vr_set_query_target: a target of n bins (n in 1, 2, 4, 8, 16, 32, else
+ * VR_ERR_UNSUPPORTED; every h_i finite and metric in 0 .. 2, else VR_ERR_ARG; an
+ * error leaves the state as it was), copied; similarity != 0: frames of 1 - D;
+ * h == NULL clears the state.  Host state only: no device call, so it works
+ * without a GPU and before any volume is resident.
+ * vr_query_target: the target (h: room for 32 floats), its count, the metric and
+ * the flag; any argument may be NULL; VR_ERR_STATE if nothing is set.
+ * vr_set_query_target_region: query by example -- the target becomes the mean
+ * record of the box [x0, x1) x [y0, y1) x [z0, z1) of the resident record volume.
+ * The box must be non-empty, inside the volume and of at most 4096 voxels, else
+ * VR_ERR_ARG; VR_ERR_STATE without a record volume.  The records are copied to
+ * the host synchronously after the library stream has drained (pitches honoured,
+ * f16 widened); each bin is summed in double, voxel after voxel, x fastest, then
+ * y, then z, divided by the voxel count in double and rounded once to float.  The
+ * state is then that of vr_set_query_target, and vr_query_target reads it back.
+ * Every call that sets or clears the target drops the baked distance plane.
+ *
+ * vr_bake_distance: the statistic of every voxel, decoded once with the same
+ * arithmetic, into one float plane in the layout of vr_bake_stats (as
+ * vr_bake_weighted; a plane of its own, resident beside the weighted and quantile
+ * planes or without them).  While it is resident a queryMethod-12 frame is
+ * rendered from it by the plane march of vr_render (vr_last_kernel "<B=1,M=0>";
+ * M=-1: a plane beyond 32-bit indices), bit-identical to the per-step frame.
+ * Synchronous.  VR_ERR_STATE: no record volume, no target, or a target count
+ * other than the volume's bins; VR_ERR_UNSUPPORTED: more than 65535 rows or
+ * slices.  The plane is dropped by any call that sets or clears the target, a
+ * new upload or release of the volume, vr_convert_f16, vr_release_stats,
+ * freeCudaBuffers and vr_release_distance.
+ * vr_distance_info: the plane's device pointer (NULL: not baked) and its length
+ * in floats; either argument may be NULL. */
+#define VR_QUERY_DISTANCE 12
+#define VR_DIST_L1 0
+#define VR_DIST_EMD 1
+#define VR_DIST_KS 2
+int vr_set_query_target(const float *h, int n, int metric, int similarity);
+int vr_query_target(float *h, int *n, int *metric, int *similarity);
+int vr_set_query_target_region(int x0, int y0, int z0, int x1, int y1, int z1, int metric,
+                               int similarity);
+int vr_bake_distance(void);
+int vr_release_distance(void);
+int vr_distance_info(const float **d_plane, uint64_t *plane_floats);
+
 /* The range probability of GMM volumes: queryMethod 10
  * (VR_QUERY_WEIGHTED) on a GMM volume samples the mixture's mass in [lo, hi),
  *   s = sum_k w_k (Phi((hi - mu_k) / sigma_k) - Phi((lo - mu_k) / sigma_k)),

@@ -22,6 +22,10 @@ VR_DTYPE_F32 = 0
 VR_DTYPE_F16 = 1
 VR_QUERY_WEIGHTED = 10
 VR_QUERY_QUANTILE = 11
+VR_QUERY_DISTANCE = 12
+VR_DIST_L1 = 0
+VR_DIST_EMD = 1
+VR_DIST_KS = 2
 
 
 class VRError(RuntimeError):
@@ -114,6 +118,8 @@ EXPORTS = [
     "vr_bake_gmm_range", "vr_release_gmm_range", "vr_gmm_range_info",
     "vr_gmm_quantile_steps", "vr_bake_gmm_quantile", "vr_release_gmm_quantile",
     "vr_gmm_quantile_info",
+    "vr_set_query_target", "vr_query_target", "vr_set_query_target_region", "vr_bake_distance",
+    "vr_release_distance", "vr_distance_info",
 ]
 
 _lib = None
@@ -300,6 +306,18 @@ def load() -> ctypes.CDLL:
     L.vr_release_gmm_quantile.restype = i32
     L.vr_gmm_quantile_info.argtypes = [vp] * 4
     L.vr_gmm_quantile_info.restype = i32
+    L.vr_set_query_target.argtypes = [vp, i32, i32, i32]
+    L.vr_set_query_target.restype = i32
+    L.vr_query_target.argtypes = [vp] * 4
+    L.vr_query_target.restype = i32
+    L.vr_set_query_target_region.argtypes = [i32] * 8
+    L.vr_set_query_target_region.restype = i32
+    L.vr_bake_distance.argtypes = []
+    L.vr_bake_distance.restype = i32
+    L.vr_release_distance.argtypes = []
+    L.vr_release_distance.restype = i32
+    L.vr_distance_info.argtypes = [vp] * 2
+    L.vr_distance_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

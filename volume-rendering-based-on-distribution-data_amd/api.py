@@ -736,6 +736,75 @@ def quantile_info():
     return p.value, n.value
 
 
+# ---------------------- distribution-distance query (method 12)
+
+QUERY_DISTANCE = _lib.VR_QUERY_DISTANCE
+_DIST_METRICS = {"l1": _lib.VR_DIST_L1, "emd": _lib.VR_DIST_EMD, "ks": _lib.VR_DIST_KS}
+
+
+def _dist_metric(metric) -> int:
+    if isinstance(metric, str):
+        if metric.lower() not in _DIST_METRICS:
+            raise ValueError(f"metric must be one of {sorted(_DIST_METRICS)}, got {metric!r}")
+        return _DIST_METRICS[metric.lower()]
+    return int(metric)
+
+
+def set_query_target(h, metric="l1", similarity=False) -> None:
+    """Set the target record of query method 12, the distance D(p, h) of every
+    voxel's record p from h (1, 2, 4, 8, 16 or 32 finite floats, one per bin of the
+    record volume) under metric "l1" (total variation), "emd" (earth mover's on the
+    value axis [0, 1]) or "ks" (largest CDF gap); similarity: frames of 1 - D.
+    None clears it.  Host state only; a baked distance plane is dropped."""
+    L = _lib.load()
+    if h is None:
+        check(L.vr_set_query_target(None, 0, 0, 0))
+        return
+    a = np.ascontiguousarray(np.asarray(h, dtype=np.float32).reshape(-1))
+    check(L.vr_set_query_target(a.ctypes.data, int(a.size), _dist_metric(metric),
+                                int(bool(similarity))))
+
+
+def query_target():
+    """(h, metric, similarity) as set: the target (float32 array), the metric's
+    name and the flag; VRError (VR_ERR_STATE) if nothing is set."""
+    h = np.zeros(32, np.float32)
+    n, m, s = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().vr_query_target(h.ctypes.data, ctypes.addressof(n), ctypes.addressof(m),
+                                      ctypes.addressof(s)))
+    name = {v: k for k, v in _DIST_METRICS.items()}[m.value]
+    return h[:n.value].copy(), name, bool(s.value)
+
+
+def set_query_target_region(lo, hi, metric="l1", similarity=False) -> None:
+    """Query by example: the target becomes the mean record of the box
+    [lo, hi) = [x0, x1) x [y0, y1) x [z0, z1) of the resident record volume (at most
+    4096 voxels; vr_set_query_target_region).  query_target() reads it back."""
+    x0, y0, z0 = (int(v) for v in lo)
+    x1, y1, z1 = (int(v) for v in hi)
+    check(_lib.load().vr_set_query_target_region(x0, y0, z0, x1, y1, z1, _dist_metric(metric),
+                                                 int(bool(similarity))))
+
+
+def bake_distance() -> None:
+    """Decode the distance statistic of every voxel once into a float plane
+    (vr_bake_distance, synchronous); method-12 frames then read the plane,
+    bit-identical to the per-step frames, until the target or the volume change."""
+    check(_lib.load().vr_bake_distance())
+
+
+def release_distance() -> None:
+    """Drop the baked distance plane: method 12 decodes the records per step again."""
+    check(_lib.load().vr_release_distance())
+
+
+def distance_info():
+    """(plane_ptr, plane_floats) of the baked distance plane; plane_ptr None = not baked"""
+    p, n = ctypes.c_void_p(), ctypes.c_uint64()
+    check(_lib.load().vr_distance_info(ctypes.addressof(p), ctypes.addressof(n)))
+    return p.value, n.value
+
+
 # ------------------- range probability of GMM volumes (method 10, DESIGN.md section 18)
 
 def set_gmm_range(lo: float, hi: float) -> None:
@@ -849,6 +918,8 @@ __all__ = [
     "bake_weighted", "release_weighted", "weighted_info",
     "QUERY_QUANTILE", "set_quantile", "set_quantile_spread", "quantile", "bake_quantile",
     "release_quantile", "quantile_info",
+    "QUERY_DISTANCE", "set_query_target", "query_target", "set_query_target_region",
+    "bake_distance", "release_distance", "distance_info",
     "set_gmm_range", "clear_gmm_range", "gmm_range", "gmm_phi_table", "bake_gmm_range",
     "release_gmm_range", "gmm_range_info",
     "gmm_quantile_steps", "bake_gmm_quantile", "release_gmm_quantile", "gmm_quantile_info",

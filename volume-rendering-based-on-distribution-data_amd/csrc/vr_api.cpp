@@ -117,6 +117,14 @@ struct State {
     int qmode = 0;
     float *qstats = nullptr;
     uint64_t qplane = 0, qsy = 0, qsz = 0;
+    // distribution-distance query (method 12, vr_distance.hip, DESIGN.md section
+    // 20): the target record and the similarity flag (dn = 0: none set; host
+    // state), the metric, and the plane vr_bake_distance made of them, a plane of
+    // its own
+    vr::DistTarget dt = {};
+    int dn = 0, dmetric = 0;
+    float *dstats = nullptr;
+    uint64_t dplane = 0, dsy = 0, dsz = 0;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -202,10 +210,22 @@ void release_quantile() {
     g.qplane = 0;
 }
 
+// the baked distance plane (vr_release_distance; with the records' other planes;
+// on any call that sets or clears the target)
+void release_distance() {
+    if (g.dstats) {
+        (void)hipFree(g.dstats);
+        g.volume_epoch++;
+    }
+    g.dstats = nullptr;
+    g.dplane = 0;
+}
+
 void release_stats() {
     release_plane_copies();  // copies of the planes go with them
     release_weighted();      // derived from the same records
     release_quantile();
+    release_distance();
     if (g.stats) (void)hipFree(g.stats);
     g.stats = nullptr;
     g.stats_plane = 0;
@@ -380,6 +400,21 @@ int check_method(int m) {
         if (g.qmode == 0)
             return fail(VR_ERR_STATE, "queryMethod %d needs a quantile (vr_set_quantile / "
                                       "vr_set_quantile_spread)", m);
+        return VR_OK;
+    }
+    if (m == VR_QUERY_DISTANCE) {
+        if (!g.vol)
+            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
+                                      "vr_init_distribution*)", m);
+        if (!lin_bins(g.nb))
+            return fail(VR_ERR_UNSUPPORTED, "the distance query on records of %d bins "
+                                            "(compiled: 1,2,4,8,16,32)", g.nb);
+        if (g.dn == 0)
+            return fail(VR_ERR_STATE, "queryMethod %d needs a target (vr_set_query_target / "
+                                      "vr_set_query_target_region)", m);
+        if (g.dn != g.nb)
+            return fail(VR_ERR_STATE, "a target of %d bins is set, the resident records have %d "
+                                      "bins", g.dn, g.nb);
         return VR_OK;
     }
     if (is_flex_method(m)) {
@@ -1637,7 +1672,8 @@ void apply_plan(const vr::MarchPlan &pl, vr::Params &P) {
 }
 
 // a frame from a plane of one float per voxel baked from the records (the
-// weighted plane, the quantile plane) in x-row bricks of pitches psy / psz
+// weighted plane, the quantile plane, the distance plane) in x-row bricks of
+// pitches psy / psz
 int launch_record_plane(const vr_render_desc *desc, vr::Params &P, uint32_t nslots,
                         const float *plane, uint64_t psy, uint64_t psz, hipError_t &e) {
     vr::PlanIn in = {};
@@ -1700,6 +1736,17 @@ int launch_quantile(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, 
     return launch_record_plane(desc, P, nslots, g.qstats, g.qsy, g.qsz, e);
 }
 
+// The march of a distance frame (method 12; check_method has passed), shaped like
+// launch_weighted: k_march_dist per step, the plane march once vr_bake_distance
+// has made the plane.
+int launch_distance(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
+    if (!g.dstats) {
+        e = vr::launch_march_dist(g.vol, is_f16(), P, g.dt, g.dmetric, nslots, g.stream);
+        return VR_OK;
+    }
+    return launch_record_plane(desc, P, nslots, g.dstats, g.dsy, g.dsz, e);
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -1746,6 +1793,10 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     } else if (qm == VR_QUERY_QUANTILE) {
         if (dry) return VR_OK;
         rc = launch_quantile(desc, P, nslots, e);
+        if (rc != VR_OK) return rc;
+    } else if (qm == VR_QUERY_DISTANCE) {
+        if (dry) return VR_OK;
+        rc = launch_distance(desc, P, nslots, e);
         if (rc != VR_OK) return rc;
     } else {
         // records (fp32 / f16) and baked planes: vr_plan.cpp chooses the march
@@ -1836,7 +1887,8 @@ int vr_debug_box_check(uint64_t *d_buf) {
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
     if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||  // no counting instance of
-                 desc->query_method == VR_QUERY_QUANTILE))   // k_march_lin / k_march_quant
+                 desc->query_method == VR_QUERY_QUANTILE ||  // k_march_lin / k_march_quant /
+                 desc->query_method == VR_QUERY_DISTANCE))   // k_march_dist
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
     uint32_t nslots = 0;
@@ -1867,7 +1919,8 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
     if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||
-                 desc->query_method == VR_QUERY_QUANTILE))
+                 desc->query_method == VR_QUERY_QUANTILE ||
+                 desc->query_method == VR_QUERY_DISTANCE))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
     uint32_t nslots = 0;
@@ -2861,6 +2914,144 @@ int vr_release_quantile(void) {
 int vr_quantile_info(const float **d_plane, uint64_t *plane_floats) {
     if (d_plane) *d_plane = g.qstats;
     if (plane_floats) *plane_floats = g.qplane;
+    return VR_OK;
+}
+
+// ---------------- distribution-distance query (method 12) ----
+
+int vr_set_query_target(const float *h, int n, int metric, int similarity) {
+    if (!h) {  // clear
+        release_distance();
+        g.dn = 0;
+        g.dmetric = 0;
+        g.dt = vr::DistTarget{};
+        return VR_OK;
+    }
+    if (!lin_bins(n))
+        return fail(VR_ERR_UNSUPPORTED, "a target of %d bins (supported: 1,2,4,8,16,32)", n);
+    if (metric < VR_DIST_L1 || metric > VR_DIST_KS)
+        return fail(VR_ERR_ARG, "unknown distance metric %d (VR_DIST_L1 / _EMD / _KS)", metric);
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(h[i])) return fail(VR_ERR_ARG, "target bin %d is not finite", i);
+    release_distance();  // a plane baked against another target
+    vr::DistTarget t = {};
+    std::memcpy(t.h, h, (size_t)n * sizeof(float));  // (h may be g.dt.h itself)
+    t.similarity = similarity != 0;
+    g.dt = t;
+    g.dn = n;
+    g.dmetric = metric;
+    return VR_OK;
+}
+
+int vr_query_target(float *h, int *n, int *metric, int *similarity) {
+    if (g.dn == 0) return fail(VR_ERR_STATE, "no query target set");
+    if (h) std::memcpy(h, g.dt.h, (size_t)g.dn * sizeof(float));
+    if (n) *n = g.dn;
+    if (metric) *metric = g.dmetric;
+    if (similarity) *similarity = g.dt.similarity;
+    return VR_OK;
+}
+
+int vr_set_query_target_region(int x0, int y0, int z0, int x1, int y1, int z1, int metric,
+                               int similarity) {
+    constexpr int64_t kMaxVoxels = 4096;
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
+    if (x0 < 0 || y0 < 0 || z0 < 0 || x1 > g.nx || y1 > g.ny || z1 > g.nz || x0 >= x1 ||
+        y0 >= y1 || z0 >= z1)
+        return fail(VR_ERR_ARG, "vr_set_query_target_region: the box must be non-empty and inside "
+                                "the %d x %d x %d volume", g.nx, g.ny, g.nz);
+    const int64_t bx = x1 - x0, by = y1 - y0, bz = z1 - z0;
+    if (bx * by * bz > kMaxVoxels)
+        return fail(VR_ERR_ARG, "vr_set_query_target_region: a box of %lld voxels (at most %lld)",
+                    (long long)(bx * by * bz), (long long)kMaxVoxels);
+    if (!lin_bins(g.nb))
+        return fail(VR_ERR_UNSUPPORTED, "a target of %d bins (supported: 1,2,4,8,16,32)", g.nb);
+    if (metric < VR_DIST_L1 || metric > VR_DIST_KS)
+        return fail(VR_ERR_ARG, "unknown distance metric %d (VR_DIST_L1 / _EMD / _KS)", metric);
+    // the box's records to the host, row by row of each slice, once the library
+    // stream has drained (a bake or a conversion may still be writing)
+    const size_t rec = (size_t)g.nb * elem_bytes();
+    std::vector<char> box((size_t)(bx * by * bz) * rec);
+    VR_HIP(hipStreamSynchronize(g.stream));
+    const char *src = reinterpret_cast<const char *>(g.vol);
+    for (int64_t z = 0; z < bz; z++) {
+        const uint64_t first = (uint64_t)(z0 + z) * g.sz + (uint64_t)y0 * g.sy + (uint64_t)x0;
+        VR_HIP(hipMemcpy2D(box.data() + (size_t)(z * by * bx) * rec, (size_t)bx * rec,
+                           src + first * rec, g.sy * rec, (size_t)bx * rec, (size_t)by,
+                           hipMemcpyDeviceToHost));
+    }
+    // each bin summed in double, voxel after voxel (x fastest, then y, then z),
+    // divided by the count in double and rounded once to float
+    double sum[32] = {};
+    const int64_t nvox = bx * by * bz;
+    for (int64_t v = 0; v < nvox; v++) {
+        const char *r = box.data() + (size_t)v * rec;
+        for (int i = 0; i < g.nb; i++) {
+            if (g.dtype == VR_DTYPE_F16) {
+                _Float16 hv;
+                std::memcpy(&hv, r + 2 * (size_t)i, 2);
+                sum[i] += (double)(float)hv;  // widened exactly
+            } else {
+                float fv;
+                std::memcpy(&fv, r + 4 * (size_t)i, 4);
+                sum[i] += (double)fv;
+            }
+        }
+    }
+    float h[32] = {};
+    for (int i = 0; i < g.nb; i++) h[i] = (float)(sum[i] / (double)nvox);
+    return vr_set_query_target(h, g.nb, metric, similarity);
+}
+
+int vr_bake_distance(void) {
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
+    if (g.dn == 0)
+        return fail(VR_ERR_STATE, "no query target set (vr_set_query_target / "
+                                  "vr_set_query_target_region)");
+    if (g.dn != g.nb)
+        return fail(VR_ERR_STATE, "a target of %d bins is set, the resident records have %d bins",
+                    g.dn, g.nb);
+    if (g.dstats) return VR_OK;  // baked against this target: any change drops the plane
+    vr::Params P;
+    std::memset(&P, 0, sizeof P);
+    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
+    P.sy = g.sy; P.sz = g.sz;
+    P.nb = g.nb;
+    uint64_t psy = 0, psz = 0;
+    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
+    const uint64_t plane = psz * (uint64_t)g.nz;
+    float *buf = nullptr;
+    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
+    // (the plane's padding is read with weight 0: it must hold finite floats)
+    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
+    if (e == hipSuccess)
+        e = vr::launch_bake_dist(g.vol, is_f16(), P, g.dt, g.dmetric, buf, psy, psz, g.stream);
+    // synchronous, like vr_bake_stats: a later frame may run on another stream
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(g.stream);
+        (void)hipFree(buf);
+        if (e == hipErrorInvalidValue)
+            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
+                                            "slices)", g.nx, g.ny, g.nz);
+        return hip_fail(e, "vr_bake_distance(k_bake_dist)");
+    }
+    g.dstats = buf;
+    g.dplane = plane;
+    g.dsy = psy;
+    g.dsz = psz;
+    g.volume_epoch++;
+    return VR_OK;
+}
+
+int vr_release_distance(void) {
+    release_distance();
+    return VR_OK;
+}
+
+int vr_distance_info(const float **d_plane, uint64_t *plane_floats) {
+    if (d_plane) *d_plane = g.dstats;
+    if (plane_floats) *plane_floats = g.dplane;
     return VR_OK;
 }
 

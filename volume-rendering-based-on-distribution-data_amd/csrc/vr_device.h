@@ -645,6 +645,34 @@ __device__ __forceinline__ float quant_stat(const float (&p)[B], float q_lo, flo
     }
 }
 
+// The distribution-distance query (method 12): how far the
+// record is from a target record h, uniform over the launch.  All float, every
+// operation separate, in bin order (numpy float32 restates it bit for bit), no
+// division, subnormal differences kept, nothing normalised.  d_i = p_i - h_i;
+//   METRIC 0 (L1):  a = a + |d_i|,                  D = a * 0.5
+//   METRIC 1 (EMD): e = e + d_i, a = a + |e|,       D = a * (1 / B)  (B a power of two)
+//   METRIC 2 (KS):  e = e + d_i, a = fmaxf(a, |e|), D = a
+// (fmaxf: the other operand for a NaN).  similarity: 1 - D instead of D.
+template <int B, int METRIC>
+__device__ __forceinline__ float dist_stat(const float (&p)[B], const float *h, bool similarity) {
+    static_assert((B & (B - 1)) == 0, "1 / B must be exact");
+    static_assert(METRIC >= 0 && METRIC <= 2, "L1, EMD or KS");
+    float a = 0.0f, e = 0.0f;
+#pragma unroll
+    for (int i = 0; i < B; i++) {
+        const float d = p[i] - h[i];
+        if constexpr (METRIC == 0) {
+            a = a + fabsf(d);
+        } else {
+            e = e + d;
+            if constexpr (METRIC == 1) a = a + fabsf(e);
+            else a = fmaxf(a, fabsf(e));
+        }
+    }
+    const float D = METRIC == 0 ? a * 0.5f : METRIC == 1 ? a * (1.0f / (float)B) : a;
+    return similarity ? 1.0f - D : D;
+}
+
 // record_stat with the entropy's log table in LDS (tab: copy_logtab)
 template <int B, int M>
 __device__ __forceinline__ float record_stat_p(const float (&p)[B], float enorm, const LogEnt *tab) {

@@ -199,6 +199,23 @@ hipError_t launch_march_gmm_quant(int K, bool half, const Params &P, const Quant
 hipError_t launch_bake_gmm_quant(const void *wm, const void *sg, bool half, int K, int nx, int ny,
                                  int z_base, int nzs, const QuantArgs &q, bool spread, float *out,
                                  uint64_t psy, uint64_t psz, hipStream_t s);
+// ---- distribution-distance query (method 12, vr_distance.hip) ----
+// the target record and the similarity flag of a launch: a kernel argument of
+// their own after Params (wave-uniform kernarg: scalar loads, h_i an SGPR operand
+// of the subtraction, the flag a uniform select); the first nb entries are used
+struct DistTarget {
+    float h[32];
+    int similarity;
+};
+// k_march_dist: the march of launch_march_lin with dist_stat against the target per
+// corner, metric 0 (L1), 1 (EMD) or 2 (KS); same bin counts and errors (another
+// metric: hipErrorInvalidValue); records its name for vr_last_kernel() (M=12)
+hipError_t launch_march_dist(const void *vol, bool half, const Params &P, const DistTarget &t,
+                             int metric, uint32_t nslots, hipStream_t s);
+// k_bake_dist: the same statistic of every voxel into one float plane
+// (launch_bake_lin's layout and limits)
+hipError_t launch_bake_dist(const void *vol, bool half, const Params &P, const DistTarget &t,
+                            int metric, float *out, uint64_t psy, uint64_t psz, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,

@@ -1,7 +1,8 @@
 // vr_query.h -- the per-ray pipelined march and the bake of a per-corner
 // statistic of float or _Float16 records in x rows, shared by the weighted-bin
-// query (method 10, vr_query.hip) and the quantile query (method 11,
-// vr_quantile.hip).  Only the statistic differs: a functor S with
+// query (method 10, vr_query.hip), the quantile query (method 11,
+// vr_quantile.hip) and the distribution-distance query (method 12,
+// vr_distance.hip).  Only the statistic differs: a functor S with
 //     template <typename T, int B> float operator()(const LinRec<T, B> &) const
 // uniform over the launch (its state comes from a kernel argument after Params).
 #pragma once
