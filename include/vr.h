@@ -776,6 +776,82 @@ int vr_bake_distance(void);
 int vr_release_distance(void);
 int vr_distance_info(const float **d_plane, uint64_t *plane_floats);
 
+/* The level-crossing query: queryMethod 13 samples the
+ * probability that the isosurface v = theta passes through the cell a sample lies
+ * in -- the level-crossing probability of probabilistic marching cubes.  It is the
+ * first query that is a joint function of the 8 corner distributions of a cell
+ * and not a blend of per-voxel numbers.  ASSUMPTION OF THE METHOD: the 8 corners
+ * are independent.  With F_c = P(v_c < theta) the surface crosses the cell unless
+ * all corners lie on one side of it: P = 1 - prod F_c - prod (1 - F_c).
+ * Arithmetic.  At a sample the footprint gives the 8 clamped corners the other
+ * queries fetch, c = 0 .. 7 with x = c & 1, y = c & 2, z = c & 4.  For each,
+ *   F_c = sum w_i p_i          method 10's arithmetic (a = 0; a = a + w_i * p_i in
+ *                              bin order) against the crossing weights w
+ * (f16 records widened first, which is exact), then in float, every operation
+ * separate (never fused), subnormals kept, nothing clamped:
+ *   lo = F_0;  hi = 1.0f - F_0
+ *   for c = 1 .. 7:  lo = lo * F_c;  hi = hi * (1.0f - F_c)
+ *   s = (1.0f - lo) - hi
+ * The filter weights of the footprint are not used: the sample is constant inside
+ * a cell, like a nearest-cell fetch.  In the outermost half-voxel shell of the
+ * volume the clamp makes corners coincide; the lines above run over the 8 fetched
+ * values as they are, so a coincident corner enters twice (or four or eight
+ * times).  s may come out a few ulp below 0; the transfer function clamps its
+ * argument as for every method.  numpy float32 restates all of it bit for bit.
+ * Record volumes only (fp32 or f16, owned or adopted) with 1, 2, 4, 8, 16 or 32
+ * bins; vr_render and render_kernel take the method like 1/2/3/10/11/12 (tile
+ * lists, d_output_f, d_steps, clipped coverage).  Every view marches the x rows of
+ * the records with k_march_cross (vr_last_kernel: "k_march_cross<B=..,M=13>"); no
+ * layout copy is used or made.
+ * vr_render / render_kernel with queryMethod 13: VR_ERR_STATE without a record
+ * volume, without crossing weights, or with a weight count other than the
+ * volume's bins; VR_ERR_UNSUPPORTED for records of any other bin count.
+ * vr_count_footprint and vr_footprint_bytes: VR_ERR_UNSUPPORTED.  vr_render_gmm
+ * with queryMethod 13: VR_ERR_UNSUPPORTED (no per-step GMM march is built).
+ *
+ * vr_set_crossing_weights: the weights w of the event whose probability F is (n
+ * in 1, 2, 4, 8, 16, 32, else VR_ERR_UNSUPPORTED; every weight finite, else
+ * VR_ERR_ARG; an error leaves the state as it was), copied; w == NULL clears
+ * them.  Any per-voxel probability that is linear in the bins may stand for F;
+ * the isovalue is the common case.  Host state only: no device call.  The state
+ * is apart from method 10's weights, the quantile and the distance target.
+ * vr_crossing_weights: the weights (w: room for 32 floats) and their count; either
+ * argument may be NULL; VR_ERR_STATE if none are set.
+ * vr_set_isovalue: w_i = (float)(n * max(0, min(theta, (i + 1) / n) - i / n))
+ * evaluated in double with theta the float received -- bit for bit the weights
+ * vr_set_query_range(0, theta, n) makes, so F is the histogram's CDF at theta on
+ * the normalised value axis [0, 1]; theta <= 0 gives F = 0 everywhere, theta >= 1
+ * the record's total.  theta must be finite, else VR_ERR_ARG.
+ * Every call that sets or clears the crossing weights drops the crossing plane.
+ *
+ * vr_bake_crossing: F of every voxel, decoded once by method 10's bake kernel
+ * (k_bake_lin) with the crossing weights, into one float plane in the layout of
+ * vr_bake_stats -- a plane of its own, resident beside the weighted, quantile and
+ * distance planes or without them.  While it is resident a queryMethod-13 frame
+ * is k_march_cross_plane on it (vr_last_kernel "k_march_cross_plane<B=1,M=13>"),
+ * bit-identical to the per-step frame.  Synchronous.  VR_ERR_STATE: no record
+ * volume, no weights, or a weight count other than the volume's bins;
+ * VR_ERR_UNSUPPORTED: more than 65535 rows or slices.  The plane is dropped by
+ * any call that sets or clears the crossing weights, a new upload or release of
+ * the volume, vr_convert_f16, vr_release_stats, freeCudaBuffers and
+ * vr_release_crossing; the weights are the caller's and survive all of these
+ * except a call that sets or clears them.
+ * vr_crossing_info: the plane's device pointer (NULL: not baked) and its length
+ * in floats; either argument may be NULL.
+ *
+ * GMM volumes: vr_render_gmm_baked with queryMethod 13 runs k_march_cross_plane
+ * over the resident GMM range plane (vr_bake_gmm_range).  Baked with
+ * vr_set_gmm_range(-inf, theta) that plane holds the mixture's CDF at theta, so
+ * the frame is the level-crossing probability of the GMM volume.  VR_ERR_STATE
+ * without a complete range plane. */
+#define VR_QUERY_CROSSING 13
+int vr_set_crossing_weights(const float *w, int n);
+int vr_crossing_weights(float *w, int *n);
+int vr_set_isovalue(float theta, int n);
+int vr_bake_crossing(void);
+int vr_release_crossing(void);
+int vr_crossing_info(const float **d_plane, uint64_t *plane_floats);
+
 /* The range probability of GMM volumes: queryMethod 10
  * (VR_QUERY_WEIGHTED) on a GMM volume samples the mixture's mass in [lo, hi),
  *   s = sum_k w_k (Phi((hi - mu_k) / sigma_k) - Phi((lo - mu_k) / sigma_k)),

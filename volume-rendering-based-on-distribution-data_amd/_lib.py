@@ -26,6 +26,7 @@ VR_QUERY_DISTANCE = 12
 VR_DIST_L1 = 0
 VR_DIST_EMD = 1
 VR_DIST_KS = 2
+VR_QUERY_CROSSING = 13
 
 
 class VRError(RuntimeError):
@@ -120,6 +121,8 @@ EXPORTS = [
     "vr_gmm_quantile_info",
     "vr_set_query_target", "vr_query_target", "vr_set_query_target_region", "vr_bake_distance",
     "vr_release_distance", "vr_distance_info",
+    "vr_set_crossing_weights", "vr_crossing_weights", "vr_set_isovalue", "vr_bake_crossing",
+    "vr_release_crossing", "vr_crossing_info",
 ]
 
 _lib = None
@@ -318,6 +321,18 @@ def load() -> ctypes.CDLL:
     L.vr_release_distance.restype = i32
     L.vr_distance_info.argtypes = [vp] * 2
     L.vr_distance_info.restype = i32
+    L.vr_set_crossing_weights.argtypes = [vp, i32]
+    L.vr_set_crossing_weights.restype = i32
+    L.vr_crossing_weights.argtypes = [vp, vp]
+    L.vr_crossing_weights.restype = i32
+    L.vr_set_isovalue.argtypes = [f32, i32]
+    L.vr_set_isovalue.restype = i32
+    L.vr_bake_crossing.argtypes = []
+    L.vr_bake_crossing.restype = i32
+    L.vr_release_crossing.argtypes = []
+    L.vr_release_crossing.restype = i32
+    L.vr_crossing_info.argtypes = [vp] * 2
+    L.vr_crossing_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

@@ -805,6 +805,59 @@ def distance_info():
     return p.value, n.value
 
 
+# ---------------------------- level-crossing query (method 13)
+
+QUERY_CROSSING = _lib.VR_QUERY_CROSSING
+
+
+def set_crossing_weights(w) -> None:
+    """Set the weights of query method 13: F = sum w_i p_i is the per-voxel
+    probability whose level-crossing probability 1 - prod F_c - prod (1 - F_c) over a
+    cell's 8 corners (taken as independent) the frame shows (1, 2, 4, 8, 16 or 32
+    finite floats, one per bin of the record volume); None clears them.  Host state
+    only, apart from method 10's weights; a baked crossing plane is dropped."""
+    L = _lib.load()
+    if w is None:
+        check(L.vr_set_crossing_weights(None, 0))
+        return
+    a = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))
+    check(L.vr_set_crossing_weights(a.ctypes.data, int(a.size)))
+
+
+def crossing_weights() -> np.ndarray:
+    """The crossing weights set (float32 array); VRError (VR_ERR_STATE) if none are."""
+    w = np.zeros(32, np.float32)
+    n = ctypes.c_int()
+    check(_lib.load().vr_crossing_weights(w.ctypes.data, ctypes.addressof(n)))
+    return w[:n.value].copy()
+
+
+def set_isovalue(theta: float, n: int) -> None:
+    """Set the crossing weights to the CDF at the isovalue theta for n-bin records:
+    F = P(v < theta) on the normalised value axis [0, 1] (vr_set_isovalue; the floats
+    of range_weights(0, theta, n))."""
+    check(_lib.load().vr_set_isovalue(float(theta), int(n)))
+
+
+def bake_crossing() -> None:
+    """Decode F of every voxel once into a float plane (vr_bake_crossing,
+    synchronous); method-13 frames then read the plane, bit-identical to the
+    per-step frames, until the crossing weights or the volume change."""
+    check(_lib.load().vr_bake_crossing())
+
+
+def release_crossing() -> None:
+    """Drop the baked crossing plane: method 13 decodes the records per step again."""
+    check(_lib.load().vr_release_crossing())
+
+
+def crossing_info():
+    """(plane_ptr, plane_floats) of the baked crossing plane; plane_ptr None = not baked"""
+    p, n = ctypes.c_void_p(), ctypes.c_uint64()
+    check(_lib.load().vr_crossing_info(ctypes.addressof(p), ctypes.addressof(n)))
+    return p.value, n.value
+
+
 # ------------------- range probability of GMM volumes (method 10, DESIGN.md section 18)
 
 def set_gmm_range(lo: float, hi: float) -> None:
@@ -920,6 +973,8 @@ __all__ = [
     "release_quantile", "quantile_info",
     "QUERY_DISTANCE", "set_query_target", "query_target", "set_query_target_region",
     "bake_distance", "release_distance", "distance_info",
+    "QUERY_CROSSING", "set_crossing_weights", "crossing_weights", "set_isovalue",
+    "bake_crossing", "release_crossing", "crossing_info",
     "set_gmm_range", "clear_gmm_range", "gmm_range", "gmm_phi_table", "bake_gmm_range",
     "release_gmm_range", "gmm_range_info",
     "gmm_quantile_steps", "bake_gmm_quantile", "release_gmm_quantile", "gmm_quantile_info",

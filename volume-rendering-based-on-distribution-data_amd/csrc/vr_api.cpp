@@ -125,6 +125,13 @@ struct State {
     int dn = 0, dmetric = 0;
     float *dstats = nullptr;
     uint64_t dplane = 0, dsy = 0, dsz = 0;
+    // level-crossing query (method 13, vr_crossing.hip): the
+    // crossing weights (xn = 0: none set; host state, apart from method 10's qw)
+    // and the plane of F vr_bake_crossing made of them, a plane of its own
+    vr::BinWeights xw = {};
+    int xn = 0;
+    float *xstats = nullptr;
+    uint64_t xplane = 0, xsy = 0, xsz = 0;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -221,11 +228,23 @@ void release_distance() {
     g.dplane = 0;
 }
 
+// the baked crossing plane (vr_release_crossing; with the records' other planes;
+// on any call that sets or clears the crossing weights)
+void release_crossing() {
+    if (g.xstats) {
+        (void)hipFree(g.xstats);
+        g.volume_epoch++;
+    }
+    g.xstats = nullptr;
+    g.xplane = 0;
+}
+
 void release_stats() {
     release_plane_copies();  // copies of the planes go with them
     release_weighted();      // derived from the same records
     release_quantile();
     release_distance();
+    release_crossing();
     if (g.stats) (void)hipFree(g.stats);
     g.stats = nullptr;
     g.stats_plane = 0;
@@ -415,6 +434,21 @@ int check_method(int m) {
         if (g.dn != g.nb)
             return fail(VR_ERR_STATE, "a target of %d bins is set, the resident records have %d "
                                       "bins", g.dn, g.nb);
+        return VR_OK;
+    }
+    if (m == VR_QUERY_CROSSING) {
+        if (!g.vol)
+            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
+                                      "vr_init_distribution*)", m);
+        if (!lin_bins(g.nb))
+            return fail(VR_ERR_UNSUPPORTED, "the level-crossing query on records of %d bins "
+                                            "(compiled: 1,2,4,8,16,32)", g.nb);
+        if (g.xn == 0)
+            return fail(VR_ERR_STATE, "queryMethod %d needs crossing weights (vr_set_isovalue / "
+                                      "vr_set_crossing_weights)", m);
+        if (g.xn != g.nb)
+            return fail(VR_ERR_STATE, "%d crossing weights are set, the resident records have %d "
+                                      "bins", g.xn, g.nb);
         return VR_OK;
     }
     if (is_flex_method(m)) {
@@ -1747,6 +1781,19 @@ int launch_distance(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, 
     return launch_record_plane(desc, P, nslots, g.dstats, g.dsy, g.dsz, e);
 }
 
+// The march of a level-crossing frame (method 13; check_method has passed).  Per
+// step: k_march_cross on the x rows of the records, whatever the view.  With the
+// plane of F resident (vr_bake_crossing): k_march_cross_plane on its bricks -- the
+// same eight floats into the same combine, so the same frame bit for bit.  No
+// plan: the one-lane march for every view, no layout copy.
+hipError_t launch_crossing(vr::Params &P, uint32_t nslots) {
+    if (!g.xstats) return vr::launch_march_cross(g.vol, is_f16(), P, g.xw, nslots, g.stream);
+    P.nb = 1;
+    P.sy = g.xsy;
+    P.sz = g.xsz;
+    return vr::launch_march_cross_plane(g.xstats, P, nslots, g.stream);
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -1798,6 +1845,9 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
         if (dry) return VR_OK;
         rc = launch_distance(desc, P, nslots, e);
         if (rc != VR_OK) return rc;
+    } else if (qm == VR_QUERY_CROSSING) {
+        if (dry) return VR_OK;
+        e = launch_crossing(P, nslots);
     } else {
         // records (fp32 / f16) and baked planes: vr_plan.cpp chooses the march
         if (qm == 7 && is_f16() && !g.stats)
@@ -1888,7 +1938,8 @@ int vr_debug_box_check(uint64_t *d_buf) {
 int64_t vr_count_footprint(const vr_render_desc *desc) {
     if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||  // no counting instance of
                  desc->query_method == VR_QUERY_QUANTILE ||  // k_march_lin / k_march_quant /
-                 desc->query_method == VR_QUERY_DISTANCE))   // k_march_dist
+                 desc->query_method == VR_QUERY_DISTANCE ||  // k_march_dist / k_march_cross
+                 desc->query_method == VR_QUERY_CROSSING))
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
     uint32_t nslots = 0;
@@ -1920,7 +1971,8 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
     if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||
                  desc->query_method == VR_QUERY_QUANTILE ||
-                 desc->query_method == VR_QUERY_DISTANCE))
+                 desc->query_method == VR_QUERY_DISTANCE ||
+                 desc->query_method == VR_QUERY_CROSSING))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
     uint32_t nslots = 0;
@@ -2537,16 +2589,20 @@ int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_f
 // A frame of method 1 / 2 from the baked GMM planes: vr_render's plane march
 // (plan_march with baked planes and no layout copies) on plane method - 1;
 // method 10: the same march on the range plane; method 11: on the quantile plane.
+// Method 13: k_march_cross_plane on the range plane, read as the plane of
+// F = P(v < theta) it is after vr_set_gmm_range(-inf, theta).
 int vr_render_gmm_baked(const vr_render_desc *desc) {
     if (!desc) return fail(VR_ERR_ARG, "null render descriptor");
-    const bool range = desc->query_method == VR_QUERY_WEIGHTED;
+    const bool cross = desc->query_method == VR_QUERY_CROSSING;
+    const bool range = cross || desc->query_method == VR_QUERY_WEIGHTED;
     const bool quant = desc->query_method == VR_QUERY_QUANTILE;
     // (the plane march is planned as method 1 for the range and quantile planes:
     // each is one float per voxel like the mean's)
     const int qm = range || quant ? 1 : desc->query_method;
     if (qm != 1 && qm != 2)
         return fail(VR_ERR_UNSUPPORTED, "baked GMM frames support queryMethod 1 (mean), 2 "
-                    "(variance), 10 (range probability) and 11 (quantile)");
+                    "(variance), 10 (range probability), 11 (quantile) and 13 (level "
+                    "crossing)");
     const State::GmmStats &b = quant ? g.gquant : range ? g.grange : g.gstats;
     if (!b.buf)
         return fail(VR_ERR_STATE, quant ? "no baked GMM quantile plane (vr_bake_gmm_quantile first)"
@@ -2561,6 +2617,12 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     as_plane.query_method = qm;
     int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
+    if (cross) {  // no plan: the one-lane march on the x-row bricks for every view
+        const hipError_t e = vr::launch_march_cross_plane(b.buf, P, nslots, g.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch(k_march_cross_plane)");
+        if (P.tile_cost) g.cost_recorded = true;
+        return VR_OK;
+    }
     vr::PlanIn in = {};
     in.m0 = desc->inv_view[0];
     in.m4 = desc->inv_view[4];
@@ -3052,6 +3114,100 @@ int vr_release_distance(void) {
 int vr_distance_info(const float **d_plane, uint64_t *plane_floats) {
     if (d_plane) *d_plane = g.dstats;
     if (plane_floats) *plane_floats = g.dplane;
+    return VR_OK;
+}
+
+// ---------------- level-crossing query (method 13) ----------
+
+int vr_set_crossing_weights(const float *w, int n) {
+    if (!w) {  // clear
+        release_crossing();
+        g.xn = 0;
+        g.xw = vr::BinWeights{};
+        return VR_OK;
+    }
+    if (!lin_bins(n))
+        return fail(VR_ERR_UNSUPPORTED, "%d crossing weights (supported: 1,2,4,8,16,32)", n);
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(w[i])) return fail(VR_ERR_ARG, "crossing weight %d is not finite", i);
+    release_crossing();  // a plane baked with other weights
+    vr::BinWeights t = {};
+    std::memcpy(t.w, w, (size_t)n * sizeof(float));  // (w may be g.xw.w itself)
+    g.xw = t;
+    g.xn = n;
+    return VR_OK;
+}
+
+int vr_crossing_weights(float *w, int *n) {
+    if (g.xn == 0) return fail(VR_ERR_STATE, "no crossing weights set");
+    if (w) std::memcpy(w, g.xw.w, (size_t)g.xn * sizeof(float));
+    if (n) *n = g.xn;
+    return VR_OK;
+}
+
+int vr_set_isovalue(float theta, int n) {
+    if (!lin_bins(n))
+        return fail(VR_ERR_UNSUPPORTED, "%d crossing weights (supported: 1,2,4,8,16,32)", n);
+    if (!std::isfinite(theta)) return fail(VR_ERR_ARG, "vr_set_isovalue: theta must be finite");
+    float w[32];
+    const double h = (double)theta, dn = (double)n;
+    for (int i = 0; i < n; i++) {  // the part of [0, theta) inside bin i, in bin widths
+        const double a = (double)i / dn, b = std::min(h, ((double)i + 1.0) / dn);
+        w[i] = (float)(dn * std::max(0.0, b - a));
+    }
+    return vr_set_crossing_weights(w, n);
+}
+
+int vr_bake_crossing(void) {
+    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
+    if (g.xn == 0)
+        return fail(VR_ERR_STATE, "no crossing weights set (vr_set_isovalue / "
+                                  "vr_set_crossing_weights)");
+    if (g.xn != g.nb)
+        return fail(VR_ERR_STATE, "%d crossing weights are set, the resident records have %d bins",
+                    g.xn, g.nb);
+    if (g.xstats) return VR_OK;  // baked with these weights: any change drops the plane
+    vr::Params P;
+    std::memset(&P, 0, sizeof P);
+    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
+    P.sy = g.sy; P.sz = g.sz;
+    P.nb = g.nb;
+    uint64_t psy = 0, psz = 0;
+    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
+    const uint64_t plane = psz * (uint64_t)g.nz;
+    float *buf = nullptr;
+    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
+    // (the plane's padding is fetched beside a row's last voxel: it must be there)
+    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
+    // the plane of F is method 10's statistic of the crossing weights: k_bake_lin
+    if (e == hipSuccess)
+        e = vr::launch_bake_lin(g.vol, is_f16(), P, g.xw, buf, psy, psz, g.stream);
+    // synchronous, like vr_bake_stats: a later frame may run on another stream
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(g.stream);
+        (void)hipFree(buf);
+        if (e == hipErrorInvalidValue)
+            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
+                                            "slices)", g.nx, g.ny, g.nz);
+        return hip_fail(e, "vr_bake_crossing(k_bake_lin)");
+    }
+    g.xstats = buf;
+    g.xplane = plane;
+    g.xsy = psy;
+    g.xsz = psz;
+    g.volume_epoch++;
+    return VR_OK;
+}
+
+int vr_release_crossing(void) {
+    release_crossing();
+    return VR_OK;
+}
+
+int vr_crossing_info(const float **d_plane, uint64_t *plane_floats) {
+    if (d_plane) *d_plane = g.xstats;
+    if (plane_floats) *plane_floats = g.xplane;
     return VR_OK;
 }
 

@@ -216,6 +216,19 @@ hipError_t launch_march_dist(const void *vol, bool half, const Params &P, const 
 // (launch_bake_lin's layout and limits)
 hipError_t launch_bake_dist(const void *vol, bool half, const Params &P, const DistTarget &t,
                             int metric, float *out, uint64_t psy, uint64_t psz, hipStream_t s);
+// ---- level-crossing query (method 13, vr_crossing.hip) ----
+// k_march_cross: the march of launch_march_lin with F_c = lin_stat against the
+// crossing weights per corner and the crossing combine 1 - prod F_c - prod (1 - F_c)
+// in place of the trilinear filter; same bin counts and errors; records its name
+// for vr_last_kernel() (M=13)
+hipError_t launch_march_cross(const void *vol, bool half, const Params &P, const BinWeights &w,
+                              uint32_t nslots, hipStream_t s);
+// k_march_cross_plane: the same march and combine over a plane of F, one float per
+// voxel in 16 x 2 x 1 bricks of pitches P.sy / P.sz (P.nb = 1; the plane k_bake_lin
+// made of the crossing weights, or a GMM range plane); 32-bit plane indices where
+// they fit, 64-bit ones otherwise
+hipError_t launch_march_cross_plane(const float *plane, const Params &P, uint32_t nslots,
+                                    hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,

@@ -1,10 +1,15 @@
 // vr_query.h -- the per-ray pipelined march and the bake of a per-corner
 // statistic of float or _Float16 records in x rows, shared by the weighted-bin
 // query (method 10, vr_query.hip), the quantile query (method 11,
-// vr_quantile.hip) and the distribution-distance query (method 12,
-// vr_distance.hip).  Only the statistic differs: a functor S with
+// vr_quantile.hip), the distribution-distance query (method 12,
+// vr_distance.hip) and the level-crossing query (method 13, vr_crossing.hip).
+// The statistic differs: a functor S with
 //     template <typename T, int B> float operator()(const LinRec<T, B> &) const
 // uniform over the launch (its state comes from a kernel argument after Params).
+// What is made of a step's 8 corner statistics is a functor too,
+//     float operator()(const float (&s)[8], const Foot &) const
+// the trilinear blend (Blend8) unless a query says otherwise (method 13: a joint
+// function of the corners, CrossCombine).
 #pragma once
 #include "vr_device.h"
 #include "vr_half.h"
@@ -60,6 +65,14 @@ constexpr int lin_batch() {
     return regs <= 8 ? 8 : regs <= 16 ? 4 : 2;
 }
 
+// the trilinear filter of the 8 corner statistics (blend8, vr_march.h): the
+// default of the loops below
+struct Blend8 {
+    __device__ __forceinline__ float operator()(const float (&s)[8], const Foot &f) const {
+        return blend8(s, f);
+    }
+};
+
 // the ray of thread tid of a tile; false: outside the rendered rectangle or a
 // miss (written), nothing to march
 struct LinRay {
@@ -82,10 +95,10 @@ __device__ __forceinline__ bool lin_ray(const Params &P, uint32_t slot, uint32_t
 }
 
 // two sets of 8 corners: march_pipe_tile / march_h_tile with st per corner
-template <typename T, int B, typename S>
+template <typename T, int B, typename S, typename BL = Blend8>
 __device__ __forceinline__ int march_lin_tile(const T *__restrict__ vol, const Params &P,
                                               const S &st, uint32_t slot, uint32_t tile,
-                                              uint32_t tid) {
+                                              uint32_t tid, const BL &bl = BL{}) {
     LinRay q;
     if (!lin_ray(P, slot, tile, tid, q)) return -1;
     const Ray &r = q.r;
@@ -110,7 +123,7 @@ __device__ __forceinline__ int march_lin_tile(const T *__restrict__ vol, const P
         float s[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) s[j] = st(rc[j]);
-        const float sample = blend8(s, fc);
+        const float sample = bl(s, fc);
         n = i + 1;
         if (composite(P, sample, sx, sy, sz, sw) || !cont) {
             alive = false;
@@ -136,10 +149,10 @@ __device__ __forceinline__ int march_lin_tile(const T *__restrict__ vol, const P
 // While one batch decodes the next is in flight -- after a step's last batch, the
 // first batch of the next step's footprint, gathered unconditionally
 // (march_h32_tile's order for N = 4).
-template <typename T, int B, int N, typename S>
+template <typename T, int B, int N, typename S, typename BL = Blend8>
 __device__ __forceinline__ int march_lin_batched(const T *__restrict__ vol, const Params &P,
                                                  const S &st, uint32_t slot, uint32_t tile,
-                                                 uint32_t tid) {
+                                                 uint32_t tid, const BL &bl = BL{}) {
     static_assert(N == 1 || N == 2 || N == 4, "an even number of batches per step");
     LinRay q;
     if (!lin_ray(P, slot, tile, tid, q)) return -1;
@@ -168,7 +181,7 @@ __device__ __forceinline__ int march_lin_batched(const T *__restrict__ vol, cons
 #pragma unroll
             for (int j = 0; j < N; j++) s[k + N + j] = st(rb[j]);
         }
-        const float sample = blend8(s, fc);
+        const float sample = bl(s, fc);
         n = i + 1;
         if (composite(P, sample, sx, sy, sz, sw) || !cont) break;
         t = tn;
@@ -184,15 +197,15 @@ __device__ __forceinline__ int march_lin_batched(const T *__restrict__ vol, cons
 
 // the body of a march kernel: the tile of this workgroup, marched in batches of N
 // corners (8: the two-set loop)
-template <typename T, int B, int N, typename S>
+template <typename T, int B, int N, typename S, typename BL = Blend8>
 __device__ __forceinline__ void march_lin_kernel(const T *__restrict__ vol, const Params &P,
-                                                 const S &st) {
+                                                 const S &st, const BL &bl = BL{}) {
     const uint32_t slot = launch_slot(P);
     const uint32_t tile = tile_of(P, slot);
     if (tile == kPad) return;
     int n;
-    if constexpr (N == 8) n = march_lin_tile<T, B>(vol, P, st, slot, tile, threadIdx.x);
-    else n = march_lin_batched<T, B, N>(vol, P, st, slot, tile, threadIdx.x);
+    if constexpr (N == 8) n = march_lin_tile<T, B>(vol, P, st, slot, tile, threadIdx.x, bl);
+    else n = march_lin_batched<T, B, N>(vol, P, st, slot, tile, threadIdx.x, bl);
     if (P.tile_cost) record_tile_cost(P, tile, n);  // all lanes have reconverged here
 }
 
