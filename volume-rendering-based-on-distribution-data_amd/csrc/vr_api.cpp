@@ -94,44 +94,38 @@ struct State {
     // vr_bake_gmm_quantile made of the quantile state below (qq, qmode) -- a third
     // plane set of one plane, independent of gstats and grange
     GmmStats gquant;
+    // A baked set of planes of one float per voxel in x-row bricks (plane_pitches),
+    // one allocation: `floats` floats a plane, pitches sy / sz; buf nullptr = not
+    // baked
+    struct Planes {
+        float *buf = nullptr;
+        uint64_t floats = 0, sy = 0, sz = 0;
+    };
     // baked statistics (basicDataProcessing / vr_bake_stats, vr_stats.hip):
-    // four planes of stats_plane floats for the raw volume (methods 1/2/3 and
-    // method 7's corner mean) and
-    // of cstats_plane floats for the codec volume (methods 4/5/6); nullptr =
-    // not baked, the march decodes the records at every step
-    float *stats = nullptr, *cstats = nullptr;
-    uint64_t stats_plane = 0, cstats_plane = 0;
-    uint64_t stats_sy = 0, stats_sz = 0, cstats_sy = 0, cstats_sz = 0;  // plane_pitches
-    // weighted-bin query (method 10, vr_query.hip): the bin
-    // weights (qn = 0: none set; host state, no HIP call sets or reads them) and
-    // the plane vr_bake_weighted made of them (nullptr: the march decodes per
-    // step), wplane floats in the bricks of pitches wsy / wsz
+    // four planes for the raw volume (methods 1/2/3 and method 7's corner mean)
+    // and three for the codec volume (methods 4/5/6); not baked: the march
+    // decodes the records at every step
+    Planes stats, cstats;
+    // The record queries (methods 10-13, kRecordQueries below; DESIGN.md sections
+    // 16, 17, 20, 21).  Each has a piece of host state (no HIP call sets or reads
+    // it) and qplane[method - 10], the one plane its vr_bake_* made of that state
+    // (not baked: the march decodes per step), independent of the other three.
+    Planes qplane[4];
+    // method 10, weighted bins: the bin weights (qn = 0: none set)
     vr::BinWeights qw = {};
     int qn = 0;
-    float *wstats = nullptr;
-    uint64_t wplane = 0, wsy = 0, wsz = 0;
-    // quantile query (method 11, vr_quantile.hip): the
-    // quantiles (qmode 0: none set, 1: Q(q_lo), 2: the spread Q(q_hi) - Q(q_lo);
-    // host state) and the plane vr_bake_quantile made of them, a plane of its own
+    // method 11, quantile: the quantiles (qmode 0: none set, 1: Q(q_lo), 2: the
+    // spread Q(q_hi) - Q(q_lo))
     vr::QuantArgs qq = {};
     int qmode = 0;
-    float *qstats = nullptr;
-    uint64_t qplane = 0, qsy = 0, qsz = 0;
-    // distribution-distance query (method 12, vr_distance.hip, DESIGN.md section
-    // 20): the target record and the similarity flag (dn = 0: none set; host
-    // state), the metric, and the plane vr_bake_distance made of them, a plane of
-    // its own
+    // method 12, distribution distance: the target record and the similarity flag
+    // (dn = 0: none set), and the metric
     vr::DistTarget dt = {};
     int dn = 0, dmetric = 0;
-    float *dstats = nullptr;
-    uint64_t dplane = 0, dsy = 0, dsz = 0;
-    // level-crossing query (method 13, vr_crossing.hip): the
-    // crossing weights (xn = 0: none set; host state, apart from method 10's qw)
-    // and the plane of F vr_bake_crossing made of them, a plane of its own
+    // method 13, level crossing: the crossing weights (xn = 0: none set), apart
+    // from method 10's qw; its plane holds F
     vr::BinWeights xw = {};
     int xn = 0;
-    float *xstats = nullptr;
-    uint64_t xplane = 0, xsy = 0, xsz = 0;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -195,65 +189,30 @@ int hip_fail(hipError_t e, const char *what) {
 
 void release_plane_copies();
 
-// the baked weighted plane (vr_release_weighted; with the records' other planes;
-// on any change of the weights)
-void release_weighted() {
-    if (g.wstats) {
-        (void)hipFree(g.wstats);
-        g.volume_epoch++;  // a tile order learned on the plane march is not reused
-    }
-    g.wstats = nullptr;
-    g.wplane = 0;
-}
-
-// the baked quantile plane (vr_release_quantile; with the records' other planes;
-// on any call that sets or clears the quantile)
-void release_quantile() {
-    if (g.qstats) {
-        (void)hipFree(g.qstats);
+// Frees a baked plane of a record query (vr_release_*; with the records' other
+// planes; on any call that sets or clears the state it was baked from).  A tile
+// order learned on the plane march is not reused.
+void release_planes(State::Planes &p) {
+    if (p.buf) {
+        (void)hipFree(p.buf);
         g.volume_epoch++;
     }
-    g.qstats = nullptr;
-    g.qplane = 0;
+    p = State::Planes();
 }
 
-// the baked distance plane (vr_release_distance; with the records' other planes;
-// on any call that sets or clears the target)
-void release_distance() {
-    if (g.dstats) {
-        (void)hipFree(g.dstats);
-        g.volume_epoch++;
-    }
-    g.dstats = nullptr;
-    g.dplane = 0;
-}
-
-// the baked crossing plane (vr_release_crossing; with the records' other planes;
-// on any call that sets or clears the crossing weights)
-void release_crossing() {
-    if (g.xstats) {
-        (void)hipFree(g.xstats);
-        g.volume_epoch++;
-    }
-    g.xstats = nullptr;
-    g.xplane = 0;
-}
+static_assert(VR_QUERY_CROSSING - VR_QUERY_WEIGHTED == 3, "qplane: one plane per method 10-13");
+State::Planes &query_plane(int method) { return g.qplane[method - VR_QUERY_WEIGHTED]; }
 
 void release_stats() {
     release_plane_copies();  // copies of the planes go with them
-    release_weighted();      // derived from the same records
-    release_quantile();
-    release_distance();
-    release_crossing();
-    if (g.stats) (void)hipFree(g.stats);
-    g.stats = nullptr;
-    g.stats_plane = 0;
+    for (State::Planes &p : g.qplane) release_planes(p);  // derived from the same records
+    if (g.stats.buf) (void)hipFree(g.stats.buf);
+    g.stats = State::Planes();
 }
 
 void release_cstats() {
-    if (g.cstats) (void)hipFree(g.cstats);
-    g.cstats = nullptr;
-    g.cstats_plane = 0;
+    if (g.cstats.buf) (void)hipFree(g.cstats.buf);
+    g.cstats = State::Planes();
 }
 
 void release_brick() {
@@ -306,7 +265,7 @@ bool is_f16() { return g.vol && g.dtype == VR_DTYPE_F16; }
 uint64_t layout_budget_bytes() {
     if (g.layout_budget != UINT64_MAX) return g.layout_budget;
     const uint64_t rec = g.vol ? g.sz * (uint64_t)g.nz * g.nb * elem_bytes() : 0;
-    const uint64_t plane = g.stats ? g.stats_plane * sizeof(float) : 0;
+    const uint64_t plane = g.stats.buf ? g.stats.floats * sizeof(float) : 0;
     return 2 * (rec + rec / 8) + 3 * (plane + plane / 8) + (64ull << 20);
 }
 
@@ -392,65 +351,99 @@ bool is_flex_method(int m) { return m == 8 || m == 9 || m == 0; }
 
 bool lin_bins(int n) { return n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 32; }
 
+// The record queries: methods 10-13 on a resident record volume (vr_query.h holds
+// their device loops, each query's .hip file its functor and launchers).  What
+// differs between them on the host, one row each, in method order; everything
+// else -- the checks, the plane's life, the frame launch -- is written once below.
+struct RecordQuery {
+    int method;
+    const char *name;     // of the query, in messages
+    const char *state;    // what its setters set, in messages
+    const char *setters;
+    const char *bake;     // the bake's entry point and kernel, in messages
+    // bins of the state set: 0 none set, -1 set and bound to no bin count
+    int (*bins)();
+    // the per-step march and the bake of the plane, from the records and the state
+    hipError_t (*march)(const vr::Params &P, uint32_t nslots);
+    hipError_t (*bake_launch)(const vr::Params &P, float *out, uint64_t psy, uint64_t psz);
+    // a frame from the plane: false, the plan's plane march (the same eight floats
+    // into the same filter as per step); true, k_march_cross_plane (method 13
+    // combines the eight corners, it does not blend them)
+    bool cross_plane;
+};
+
+const RecordQuery kRecordQueries[] = {
+    {VR_QUERY_WEIGHTED, "weighted-bin", "bin weights", "vr_set_bin_weights / vr_set_query_range",
+     "vr_bake_weighted(k_bake_lin)", [] { return g.qn; },
+     [](const vr::Params &P, uint32_t nslots) {
+         return vr::launch_march_lin(g.vol, is_f16(), P, g.qw, nslots, g.stream);
+     },
+     [](const vr::Params &P, float *out, uint64_t psy, uint64_t psz) {
+         return vr::launch_bake_lin(g.vol, is_f16(), P, g.qw, out, psy, psz, g.stream);
+     },
+     false},
+    {VR_QUERY_QUANTILE, "quantile", "a quantile", "vr_set_quantile / vr_set_quantile_spread",
+     "vr_bake_quantile(k_bake_quant)", [] { return g.qmode ? -1 : 0; },
+     [](const vr::Params &P, uint32_t nslots) {
+         return vr::launch_march_quant(g.vol, is_f16(), P, g.qq, g.qmode == 2, nslots, g.stream);
+     },
+     [](const vr::Params &P, float *out, uint64_t psy, uint64_t psz) {
+         return vr::launch_bake_quant(g.vol, is_f16(), P, g.qq, g.qmode == 2, out, psy, psz,
+                                      g.stream);
+     },
+     false},
+    {VR_QUERY_DISTANCE, "distance", "a target",
+     "vr_set_query_target / vr_set_query_target_region", "vr_bake_distance(k_bake_dist)",
+     [] { return g.dn; },
+     [](const vr::Params &P, uint32_t nslots) {
+         return vr::launch_march_dist(g.vol, is_f16(), P, g.dt, g.dmetric, nslots, g.stream);
+     },
+     [](const vr::Params &P, float *out, uint64_t psy, uint64_t psz) {
+         return vr::launch_bake_dist(g.vol, is_f16(), P, g.dt, g.dmetric, out, psy, psz, g.stream);
+     },
+     false},
+    // (the plane of F is method 10's statistic of the crossing weights: k_bake_lin)
+    {VR_QUERY_CROSSING, "level-crossing", "crossing weights",
+     "vr_set_isovalue / vr_set_crossing_weights", "vr_bake_crossing(k_bake_lin)",
+     [] { return g.xn; },
+     [](const vr::Params &P, uint32_t nslots) {
+         return vr::launch_march_cross(g.vol, is_f16(), P, g.xw, nslots, g.stream);
+     },
+     [](const vr::Params &P, float *out, uint64_t psy, uint64_t psz) {
+         return vr::launch_bake_lin(g.vol, is_f16(), P, g.xw, out, psy, psz, g.stream);
+     },
+     true},
+};
+
+// the row of method m; nullptr: not a record query
+const RecordQuery *record_query(int m) {
+    for (const RecordQuery &q : kRecordQueries)
+        if (q.method == m) return &q;
+    return nullptr;
+}
+
+// What a frame of query q and the bake of its plane both need: a record volume
+// of a compiled bin count, and the query's state, set for that bin count.
+int query_ready(const RecordQuery &q) {
+    if (!g.vol)
+        return fail(VR_ERR_STATE, "the %s query (queryMethod %d) needs a record volume (initCuda / "
+                                  "vr_init_distribution*)", q.name, q.method);
+    if (!lin_bins(g.nb))
+        return fail(VR_ERR_UNSUPPORTED, "the %s query on records of %d bins (compiled: "
+                                        "1,2,4,8,16,32)", q.name, g.nb);
+    const int n = q.bins();
+    if (n == 0)
+        return fail(VR_ERR_STATE, "the %s query (queryMethod %d) needs %s (%s)", q.name, q.method,
+                    q.state, q.setters);
+    if (n > 0 && n != g.nb)
+        return fail(VR_ERR_STATE, "the %s query: %s of %d bins set, the resident records have %d "
+                                  "bins", q.name, q.state, n, g.nb);
+    return VR_OK;
+}
+
 int check_method(int m) {
     if (m == 1 || m == 2 || m == 3 || m == 7 || m == 4 || m == 5 || m == 6) return VR_OK;
-    if (m == VR_QUERY_WEIGHTED) {
-        if (!g.vol)
-            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
-                                      "vr_init_distribution*)", m);
-        if (!lin_bins(g.nb))
-            return fail(VR_ERR_UNSUPPORTED, "the weighted-bin query on records of %d bins "
-                                            "(compiled: 1,2,4,8,16,32)", g.nb);
-        if (g.qn == 0)
-            return fail(VR_ERR_STATE, "queryMethod %d needs bin weights (vr_set_bin_weights / "
-                                      "vr_set_query_range)", m);
-        if (g.qn != g.nb)
-            return fail(VR_ERR_STATE, "%d bin weights are set, the resident records have %d bins",
-                        g.qn, g.nb);
-        return VR_OK;
-    }
-    if (m == VR_QUERY_QUANTILE) {
-        if (!g.vol)
-            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
-                                      "vr_init_distribution*)", m);
-        if (!lin_bins(g.nb))
-            return fail(VR_ERR_UNSUPPORTED, "the quantile query on records of %d bins "
-                                            "(compiled: 1,2,4,8,16,32)", g.nb);
-        if (g.qmode == 0)
-            return fail(VR_ERR_STATE, "queryMethod %d needs a quantile (vr_set_quantile / "
-                                      "vr_set_quantile_spread)", m);
-        return VR_OK;
-    }
-    if (m == VR_QUERY_DISTANCE) {
-        if (!g.vol)
-            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
-                                      "vr_init_distribution*)", m);
-        if (!lin_bins(g.nb))
-            return fail(VR_ERR_UNSUPPORTED, "the distance query on records of %d bins "
-                                            "(compiled: 1,2,4,8,16,32)", g.nb);
-        if (g.dn == 0)
-            return fail(VR_ERR_STATE, "queryMethod %d needs a target (vr_set_query_target / "
-                                      "vr_set_query_target_region)", m);
-        if (g.dn != g.nb)
-            return fail(VR_ERR_STATE, "a target of %d bins is set, the resident records have %d "
-                                      "bins", g.dn, g.nb);
-        return VR_OK;
-    }
-    if (m == VR_QUERY_CROSSING) {
-        if (!g.vol)
-            return fail(VR_ERR_STATE, "queryMethod %d needs a record volume (initCuda / "
-                                      "vr_init_distribution*)", m);
-        if (!lin_bins(g.nb))
-            return fail(VR_ERR_UNSUPPORTED, "the level-crossing query on records of %d bins "
-                                            "(compiled: 1,2,4,8,16,32)", g.nb);
-        if (g.xn == 0)
-            return fail(VR_ERR_STATE, "queryMethod %d needs crossing weights (vr_set_isovalue / "
-                                      "vr_set_crossing_weights)", m);
-        if (g.xn != g.nb)
-            return fail(VR_ERR_STATE, "%d crossing weights are set, the resident records have %d "
-                                      "bins", g.xn, g.nb);
-        return VR_OK;
-    }
+    if (const RecordQuery *q = record_query(m)) return query_ready(*q);
     if (is_flex_method(m)) {
         if (!g.flex.blocks)
             return fail(VR_ERR_STATE,
@@ -787,37 +780,58 @@ int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
     return fill_frame_params(d, v, P, nslots, for_render);
 }
 
+// Bakes n planes of the P.nx x P.ny x P.nz grid into dst: launch(buf, plane floats,
+// psy, psz) fills a zeroed buffer on the library's stream.  Synchronous: a later
+// frame may run on another stream.  On a failure nothing changes (dst keeps what
+// it held, the march keeps decoding per step): the stream drains before the
+// buffer is freed, and a launch that has no kernel for the grid or the bin count
+// (hipErrorInvalidValue) is VR_ERR_UNSUPPORTED.  `what` names the entry point and
+// kernel, `vols` the volumes, in messages.
+template <typename Launch>
+int bake_planes(State::Planes &dst, int n, const vr::Params &P, const char *what,
+                const char *vols, Launch launch) {
+    State::Planes p;
+    vr::plane_pitches((uint32_t)P.nx, (uint32_t)P.ny, p.sy, p.sz);
+    p.floats = p.sz * (uint64_t)P.nz;
+    // (4 floats of padding: a march fetches them beside a row's last voxel and
+    // reads them with weight 0, so they must be there and hold finite floats)
+    const size_t bytes = ((uint64_t)n * p.floats + 4) * sizeof(float);
+    VR_HIP(hipMalloc(&p.buf, bytes));
+    hipError_t e = hipMemsetAsync(p.buf, 0, bytes, g.stream);
+    if (e == hipSuccess) e = launch(p.buf, p.floats, p.sy, p.sz);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(g.stream);
+        (void)hipFree(p.buf);
+        if (e == hipErrorInvalidValue)
+            return fail(VR_ERR_UNSUPPORTED, "baking %s with %d bins, %d x %d x %d voxels (compiled: "
+                                            "1,2,4,8,16,32 bins; at most 65535 rows and slices)",
+                        vols, P.nb, P.nx, P.ny, P.nz);
+        return hip_fail(e, what);
+    }
+    dst = p;
+    return VR_OK;
+}
+
 // Bakes the statistics planes of the resident raw and codec volumes (whichever
-// are resident and not yet baked).  On an allocation failure nothing changes:
-// the march keeps decoding records per step.
+// are resident and not yet baked).
 int bake_stats() {
     if (!g.vol && !g.cb) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
     vr::Params P;
-    std::memset(&P, 0, sizeof P);
-    if (g.vol && !g.stats) {
+    if (g.vol && !g.stats.buf) {
+        std::memset(&P, 0, sizeof P);
         P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
         P.sy = g.sy; P.sz = g.sz;
         P.nb = g.nb;
         P.enorm = entropy_norm(g.nb);
-        uint64_t psy = 0, psz = 0;
-        vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
-        const uint64_t plane = psz * (uint64_t)g.nz;
-        float *buf = nullptr;
-        VR_HIP(hipMalloc(&buf, (4 * plane + 4) * sizeof(float)));
-        hipError_t e = hipMemsetAsync(buf, 0, (4 * plane + 4) * sizeof(float), g.stream);
-        if (e == hipSuccess)
-            e = vr::launch_bake_raw(g.vol, is_f16(), P, buf, plane, psy, psz, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            return hip_fail(e, "basicDataProcessing(k_bake_raw)");
-        }
-        g.stats = buf;
-        g.stats_plane = plane;
-        g.stats_sy = psy;
-        g.stats_sz = psz;
+        const int rc = bake_planes(
+            g.stats, 4, P, "basicDataProcessing(k_bake_raw)", "record volumes",
+            [&](float *out, uint64_t plane, uint64_t psy, uint64_t psz) {
+                return vr::launch_bake_raw(g.vol, is_f16(), P, out, plane, psy, psz, g.stream);
+            });
+        if (rc != VR_OK) return rc;
     }
-    if (g.cb && !g.cstats) {
+    if (g.cb && !g.cstats.buf) {
         std::memset(&P, 0, sizeof P);
         P.nx = g.cnx; P.ny = g.cny; P.nz = g.cnz;
         P.sy = (uint64_t)g.cnx;
@@ -829,26 +843,34 @@ int bake_stats() {
         P.err = g.cerr;
         P.ntpl = g.ntpl;
         P.err_slots = g.err_slots;
-        uint64_t psy = 0, psz = 0;
-        vr::plane_pitches((uint32_t)g.cnx, (uint32_t)g.cny, psy, psz);
-        const uint64_t plane = psz * (uint64_t)g.cnz;
-        float *buf = nullptr;
-        VR_HIP(hipMalloc(&buf, (3 * plane + 4) * sizeof(float)));
-        hipError_t e = hipMemsetAsync(buf, 0, (3 * plane + 4) * sizeof(float), g.stream);
-        if (e == hipSuccess) e = vr::launch_bake_codec(P, buf, plane, psy, psz, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            if (e == hipErrorInvalidValue)
-                return fail(VR_ERR_UNSUPPORTED, "baking codec volumes with %d bins", g.cnb);
-            return hip_fail(e, "basicDataProcessing(k_bake_codec)");
-        }
-        g.cstats = buf;
-        g.cstats_plane = plane;
-        g.cstats_sy = psy;
-        g.cstats_sz = psz;
+        const int rc = bake_planes(
+            g.cstats, 3, P, "basicDataProcessing(k_bake_codec)", "codec volumes",
+            [&](float *out, uint64_t plane, uint64_t psy, uint64_t psz) {
+                return vr::launch_bake_codec(P, out, plane, psy, psz, g.stream);
+            });
+        if (rc != VR_OK) return rc;
     }
     return VR_OK;
+}
+
+// vr_bake_*: the plane of query q from the records and q's state.  A plane that
+// is there was baked from this state (any change drops it): nothing to do.
+int bake_query(const RecordQuery &q) {
+    const int rc = query_ready(q);
+    if (rc != VR_OK) return rc;
+    State::Planes &dst = query_plane(q.method);
+    if (dst.buf) return VR_OK;
+    vr::Params P;
+    std::memset(&P, 0, sizeof P);
+    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
+    P.sy = g.sy; P.sz = g.sz;
+    P.nb = g.nb;
+    const int rb = bake_planes(dst, 1, P, q.bake, "record volumes",
+                               [&](float *out, uint64_t, uint64_t psy, uint64_t psz) {
+                                   return q.bake_launch(P, out, psy, psz);
+                               });
+    if (rb == VR_OK) g.volume_epoch++;  // a tile order learned on the per-step march is not reused
+    return rb;
 }
 
 // ---- synthetic volume tables ----
@@ -986,7 +1008,7 @@ bool ensure_plane_copy(int plane, int axis) {
     if (const char *e = vr::tuning(axis == 3 ? "VR_PLANE8" : "VR_ZROWS"))
         if (std::atoi(e) == 0) return false;
     const int i = axis - 1;
-    if (!g.stats || plane < 0 || plane > 2) return false;
+    if (!g.stats.buf || plane < 0 || plane > 2) return false;
     if (g.pcopy[i][plane].buf) return true;
     const uint32_t nf = axis == 2 ? g.nz : g.ny, np = axis == 2 ? g.ny : g.nx;
     uint64_t ns = axis == 2 ? (uint64_t)g.nx : (uint64_t)g.nz;
@@ -1013,11 +1035,11 @@ bool ensure_plane_copy(int plane, int axis) {
         return false;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    const float *src = g.stats + (uint64_t)plane * g.stats_plane;
+    const float *src = g.stats.buf + (uint64_t)plane * g.stats.floats;
     if (hipMemsetAsync(buf, 0, bytes, g.stream) != hipSuccess ||
-        (axis == 3 ? vr::launch_plane8(src, g.stats_sy, g.stats_sz, buf, dsy, dsz, g.nx, g.ny,
+        (axis == 3 ? vr::launch_plane8(src, g.stats.sy, g.stats.sz, buf, dsy, dsz, g.nx, g.ny,
                                        g.nz, g.stream)
-                   : vr::launch_plane_axis(src, g.stats_sy, g.stats_sz, buf, dsy, dsz, g.nx,
+                   : vr::launch_plane_axis(src, g.stats.sy, g.stats.sz, buf, dsy, dsz, g.nx,
                                            g.ny, g.nz, axis, g.stream)) != hipSuccess ||
         hipStreamSynchronize(g.stream) != hipSuccess) {
         (void)hipGetLastError();
@@ -1676,9 +1698,9 @@ vr::PlanIn plan_input(const vr_render_desc *d, const vr::Params &P, bool count) 
     in.nz = P.nz;
     in.owned = !codec && g.owned;
     in.f16 = !codec && is_f16();
-    in.baked = (codec ? g.cstats : g.stats) != nullptr;
-    in.plane_sy = codec ? g.cstats_sy : g.stats_sy;
-    in.plane_sz = codec ? g.cstats_sz : g.stats_sz;
+    in.baked = (codec ? g.cstats.buf : g.stats.buf) != nullptr;
+    in.plane_sy = codec ? g.cstats.sy : g.stats.sy;
+    in.plane_sz = codec ? g.cstats.sz : g.stats.sz;
     in.m7x = P.m7x;
     in.m7y = P.m7y;
     in.m7z = P.m7z;
@@ -1745,53 +1767,26 @@ int launch_record_plane(const vr_render_desc *desc, vr::Params &P, uint32_t nslo
     return VR_OK;
 }
 
-// The march of a weighted-bin frame (method 10; check_method has passed).  Per
-// step: k_march_lin on the x rows of the records, whatever the view -- no plan, no
-// layout copy.  With the baked plane resident (vr_bake_weighted): the plane march
-// plan_march names for one float per voxel in x-row bricks, the route of
-// vr_render_gmm_baked -- the same eight floats into the same filter, so the same
-// frame bit for bit.
-int launch_weighted(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
-    if (!g.wstats) {
-        e = vr::launch_march_lin(g.vol, is_f16(), P, g.qw, nslots, g.stream);
+// The march of a frame of record query q (check_method has passed).  Per step:
+// q's kernel on the x rows of the records, whatever the view -- no plan, no layout
+// copy.  With q's baked plane resident (vr_bake_*): the plane march plan_march
+// names for one float per voxel in x-row bricks, the route of vr_render_gmm_baked
+// -- the same eight floats into the same filter, so the same frame bit for bit.
+// Method 13 combines its eight corners where the others blend them: its plane of
+// F goes to k_march_cross_plane, the one-lane march for every view, no plan.
+int launch_query(const RecordQuery &q, const vr_render_desc *desc, vr::Params &P,
+                 uint32_t nslots, hipError_t &e) {
+    const State::Planes &pl = query_plane(q.method);
+    if (!pl.buf) {
+        e = q.march(P, nslots);
         return VR_OK;
     }
-    return launch_record_plane(desc, P, nslots, g.wstats, g.wsy, g.wsz, e);
-}
-
-// The march of a quantile frame (method 11; check_method has passed), shaped like
-// launch_weighted: k_march_quant per step, the plane march once vr_bake_quantile
-// has made the plane.
-int launch_quantile(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
-    if (!g.qstats) {
-        e = vr::launch_march_quant(g.vol, is_f16(), P, g.qq, g.qmode == 2, nslots, g.stream);
-        return VR_OK;
-    }
-    return launch_record_plane(desc, P, nslots, g.qstats, g.qsy, g.qsz, e);
-}
-
-// The march of a distance frame (method 12; check_method has passed), shaped like
-// launch_weighted: k_march_dist per step, the plane march once vr_bake_distance
-// has made the plane.
-int launch_distance(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, hipError_t &e) {
-    if (!g.dstats) {
-        e = vr::launch_march_dist(g.vol, is_f16(), P, g.dt, g.dmetric, nslots, g.stream);
-        return VR_OK;
-    }
-    return launch_record_plane(desc, P, nslots, g.dstats, g.dsy, g.dsz, e);
-}
-
-// The march of a level-crossing frame (method 13; check_method has passed).  Per
-// step: k_march_cross on the x rows of the records, whatever the view.  With the
-// plane of F resident (vr_bake_crossing): k_march_cross_plane on its bricks -- the
-// same eight floats into the same combine, so the same frame bit for bit.  No
-// plan: the one-lane march for every view, no layout copy.
-hipError_t launch_crossing(vr::Params &P, uint32_t nslots) {
-    if (!g.xstats) return vr::launch_march_cross(g.vol, is_f16(), P, g.xw, nslots, g.stream);
+    if (!q.cross_plane) return launch_record_plane(desc, P, nslots, pl.buf, pl.sy, pl.sz, e);
     P.nb = 1;
-    P.sy = g.xsy;
-    P.sz = g.xsz;
-    return vr::launch_march_cross_plane(g.xstats, P, nslots, g.stream);
+    P.sy = pl.sy;
+    P.sz = pl.sz;
+    e = vr::launch_march_cross_plane(pl.buf, P, nslots, g.stream);
+    return VR_OK;
 }
 
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
@@ -1822,7 +1817,7 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     if (is_flex_method(qm)) {
         if (dry) return VR_OK;
         e = vr::launch_march_flex(qm, P, nslots, g.stream);
-    } else if (qm >= 4 && qm <= 6 && !g.cstats) {
+    } else if (qm >= 4 && qm <= 6 && !g.cstats.buf) {
         if (dry) return VR_OK;
         // the one-lane codec march of a row-aligned view: a 16x4 pixel block per
         // wave (1024^3 x 8 1080p C0 m4 2.91 -> 2.88 ms, m5 5.26 -> 5.17, m6 7.07 ->
@@ -1833,24 +1828,13 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
         if (e == hipErrorInvalidValue)
             return fail(VR_ERR_UNSUPPORTED, "codec volumes with %d bins (compiled: 1,2,4,8,16,32)",
                         P.nb);
-    } else if (qm == VR_QUERY_WEIGHTED) {
+    } else if (const RecordQuery *q = record_query(qm)) {
         if (dry) return VR_OK;
-        rc = launch_weighted(desc, P, nslots, e);
+        rc = launch_query(*q, desc, P, nslots, e);
         if (rc != VR_OK) return rc;
-    } else if (qm == VR_QUERY_QUANTILE) {
-        if (dry) return VR_OK;
-        rc = launch_quantile(desc, P, nslots, e);
-        if (rc != VR_OK) return rc;
-    } else if (qm == VR_QUERY_DISTANCE) {
-        if (dry) return VR_OK;
-        rc = launch_distance(desc, P, nslots, e);
-        if (rc != VR_OK) return rc;
-    } else if (qm == VR_QUERY_CROSSING) {
-        if (dry) return VR_OK;
-        e = launch_crossing(P, nslots);
     } else {
         // records (fp32 / f16) and baked planes: vr_plan.cpp chooses the march
-        if (qm == 7 && is_f16() && !g.stats)
+        if (qm == 7 && is_f16() && !g.stats.buf)
             return fail(VR_ERR_UNSUPPORTED, "method 7 on an f16 volume reads the baked corner "
                                             "means: basicDataProcessing / vr_bake_stats first");
         vr::PlanIn in = plan_input(desc, P, false);
@@ -1869,10 +1853,10 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
         apply_plan(pl, P);
         const void *vol = g.vol;
         if (pl.method == -7) {  // the baked corner means (plane 3)
-            vol = g.stats + 3 * g.stats_plane;
+            vol = g.stats.buf + 3 * g.stats.floats;
             P.nb = 1;
-            P.sy = g.stats_sy;
-            P.sz = g.stats_sz;
+            P.sy = g.stats.sy;
+            P.sz = g.stats.sz;
         } else if (pl.method <= 0) {
             // the method's baked plane, addressed in its bricks, or its copy for the view
             P.nb = 1;
@@ -1882,13 +1866,13 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
                 P.sy = c.sy;
                 P.sz = c.sz;
             } else if (qm <= 3) {
-                vol = g.stats + (uint64_t)(qm - 1) * g.stats_plane;
-                P.sy = g.stats_sy;
-                P.sz = g.stats_sz;
+                vol = g.stats.buf + (uint64_t)(qm - 1) * g.stats.floats;
+                P.sy = g.stats.sy;
+                P.sz = g.stats.sz;
             } else {
-                vol = g.cstats + (uint64_t)(qm - 4) * g.cstats_plane;
-                P.sy = g.cstats_sy;
-                P.sz = g.cstats_sz;
+                vol = g.cstats.buf + (uint64_t)(qm - 4) * g.cstats.floats;
+                P.sy = g.cstats.sy;
+                P.sz = g.cstats.sz;
             }
         } else if (pl.axis) {
             const State::AxisCopy &c = g.acopy[pl.axis - 1];
@@ -1936,10 +1920,7 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
-    if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||  // no counting instance of
-                 desc->query_method == VR_QUERY_QUANTILE ||  // k_march_lin / k_march_quant /
-                 desc->query_method == VR_QUERY_DISTANCE ||  // k_march_dist / k_march_cross
-                 desc->query_method == VR_QUERY_CROSSING))
+    if (desc && record_query(desc->query_method))  // no counting instance of their marches
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
     uint32_t nslots = 0;
@@ -1969,10 +1950,7 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
-    if (desc && (desc->query_method == VR_QUERY_WEIGHTED ||
-                 desc->query_method == VR_QUERY_QUANTILE ||
-                 desc->query_method == VR_QUERY_DISTANCE ||
-                 desc->query_method == VR_QUERY_CROSSING))
+    if (desc && record_query(desc->query_method))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
     uint32_t nslots = 0;
@@ -2794,11 +2772,40 @@ int vr_release_stats(void) {
     return VR_OK;
 }
 
+// ---------------- the record queries (methods 10-13): shared pieces ----------------
+
+namespace {
+
+// vr_release_*
+int release_query(int method) {
+    release_planes(query_plane(method));
+    return VR_OK;
+}
+
+// vr_*_info
+int query_info(int method, const float **d_plane, uint64_t *plane_floats) {
+    const State::Planes &p = query_plane(method);
+    if (d_plane) *d_plane = p.buf;
+    if (plane_floats) *plane_floats = p.floats;
+    return VR_OK;
+}
+
+// w[i]: the part of [lo, hi) inside bin i of the n bins of [0, 1), in bin widths
+void interval_weights(float lo, float hi, int n, float *w) {
+    const double l = (double)lo, h = (double)hi, dn = (double)n;
+    for (int i = 0; i < n; i++) {
+        const double a = std::max(l, (double)i / dn), b = std::min(h, ((double)i + 1.0) / dn);
+        w[i] = (float)(dn * std::max(0.0, b - a));
+    }
+}
+
+}  // namespace
+
 // ---------------- weighted-bin query (method 10) ----------
 
 int vr_set_bin_weights(const float *w, int n) {
     if (!w) {  // clear
-        release_weighted();
+        release_planes(query_plane(VR_QUERY_WEIGHTED));
         g.qn = 0;
         g.qw = vr::BinWeights{};
         return VR_OK;
@@ -2807,7 +2814,7 @@ int vr_set_bin_weights(const float *w, int n) {
         return fail(VR_ERR_UNSUPPORTED, "%d bin weights (supported: 1,2,4,8,16,32)", n);
     for (int i = 0; i < n; i++)
         if (!std::isfinite(w[i])) return fail(VR_ERR_ARG, "bin weight %d is not finite", i);
-    release_weighted();  // a plane baked with other weights
+    release_planes(query_plane(VR_QUERY_WEIGHTED));  // a plane baked with other weights
     g.qw = vr::BinWeights{};
     std::memcpy(g.qw.w, w, (size_t)n * sizeof(float));
     g.qn = n;
@@ -2827,63 +2834,14 @@ int vr_set_query_range(float lo, float hi, int n) {
     if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi)
         return fail(VR_ERR_ARG, "vr_set_query_range: bounds must be finite with lo <= hi");
     float w[32];
-    const double l = (double)lo, h = (double)hi, dn = (double)n;
-    for (int i = 0; i < n; i++) {  // the part of [lo, hi) inside bin i, in bin widths
-        const double a = std::max(l, (double)i / dn), b = std::min(h, ((double)i + 1.0) / dn);
-        w[i] = (float)(dn * std::max(0.0, b - a));
-    }
+    interval_weights(lo, hi, n, w);
     return vr_set_bin_weights(w, n);
 }
 
-int vr_bake_weighted(void) {
-    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
-    if (g.qn == 0)
-        return fail(VR_ERR_STATE, "no bin weights set (vr_set_bin_weights / vr_set_query_range)");
-    if (g.qn != g.nb)
-        return fail(VR_ERR_STATE, "%d bin weights are set, the resident records have %d bins", g.qn,
-                    g.nb);
-    if (g.wstats) return VR_OK;  // baked with these weights: any change drops the plane
-    vr::Params P;
-    std::memset(&P, 0, sizeof P);
-    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
-    P.sy = g.sy; P.sz = g.sz;
-    P.nb = g.nb;
-    uint64_t psy = 0, psz = 0;
-    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
-    const uint64_t plane = psz * (uint64_t)g.nz;
-    float *buf = nullptr;
-    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
-    // (the plane's padding is read with weight 0: it must hold finite floats)
-    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
-    if (e == hipSuccess)
-        e = vr::launch_bake_lin(g.vol, is_f16(), P, g.qw, buf, psy, psz, g.stream);
-    // synchronous, like vr_bake_stats: a later frame may run on another stream
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(g.stream);
-        (void)hipFree(buf);
-        if (e == hipErrorInvalidValue)
-            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
-                                            "slices)", g.nx, g.ny, g.nz);
-        return hip_fail(e, "vr_bake_weighted(k_bake_lin)");
-    }
-    g.wstats = buf;
-    g.wplane = plane;
-    g.wsy = psy;
-    g.wsz = psz;
-    g.volume_epoch++;
-    return VR_OK;
-}
-
-int vr_release_weighted(void) {
-    release_weighted();
-    return VR_OK;
-}
-
+int vr_bake_weighted(void) { return bake_query(*record_query(VR_QUERY_WEIGHTED)); }
+int vr_release_weighted(void) { return release_query(VR_QUERY_WEIGHTED); }
 int vr_weighted_info(const float **d_plane, uint64_t *plane_floats) {
-    if (d_plane) *d_plane = g.wstats;
-    if (plane_floats) *plane_floats = g.wplane;
-    return VR_OK;
+    return query_info(VR_QUERY_WEIGHTED, d_plane, plane_floats);
 }
 
 // ---------------- quantile query (method 11) ----------------
@@ -2894,7 +2852,7 @@ bool quantile_ok(float q) { return std::isfinite(q) && q >= 0.0f && q <= 1.0f; }
 
 int vr_set_quantile(float q) {
     if (!quantile_ok(q)) return fail(VR_ERR_ARG, "vr_set_quantile: q must be in [0, 1]");
-    release_quantile();  // a plane baked for another quantile
+    release_planes(query_plane(VR_QUERY_QUANTILE));  // a plane baked for another quantile
     release_gmm_quantile();
     g.qq = vr::QuantArgs{q, q};
     g.qmode = 1;
@@ -2904,7 +2862,7 @@ int vr_set_quantile(float q) {
 int vr_set_quantile_spread(float q_lo, float q_hi) {
     if (!quantile_ok(q_lo) || !quantile_ok(q_hi) || q_lo > q_hi)
         return fail(VR_ERR_ARG, "vr_set_quantile_spread: 0 <= q_lo <= q_hi <= 1 required");
-    release_quantile();
+    release_planes(query_plane(VR_QUERY_QUANTILE));
     release_gmm_quantile();
     g.qq = vr::QuantArgs{q_lo, q_hi};
     g.qmode = 2;
@@ -2912,7 +2870,7 @@ int vr_set_quantile_spread(float q_lo, float q_hi) {
 }
 
 int vr_clear_quantile(void) {
-    release_quantile();
+    release_planes(query_plane(VR_QUERY_QUANTILE));
     release_gmm_quantile();
     g.qq = vr::QuantArgs{};
     g.qmode = 0;
@@ -2927,63 +2885,17 @@ int vr_quantile(float *q_lo, float *q_hi, int *spread) {
     return VR_OK;
 }
 
-int vr_bake_quantile(void) {
-    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
-    if (g.qmode == 0)
-        return fail(VR_ERR_STATE, "no quantile set (vr_set_quantile / vr_set_quantile_spread)");
-    if (!lin_bins(g.nb))
-        return fail(VR_ERR_UNSUPPORTED, "the quantile query on records of %d bins "
-                                        "(compiled: 1,2,4,8,16,32)", g.nb);
-    if (g.qstats) return VR_OK;  // baked for this quantile: any change drops the plane
-    vr::Params P;
-    std::memset(&P, 0, sizeof P);
-    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
-    P.sy = g.sy; P.sz = g.sz;
-    P.nb = g.nb;
-    uint64_t psy = 0, psz = 0;
-    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
-    const uint64_t plane = psz * (uint64_t)g.nz;
-    float *buf = nullptr;
-    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
-    // (the plane's padding is read with weight 0: it must hold finite floats)
-    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
-    if (e == hipSuccess)
-        e = vr::launch_bake_quant(g.vol, is_f16(), P, g.qq, g.qmode == 2, buf, psy, psz,
-                                  g.stream);
-    // synchronous, like vr_bake_stats: a later frame may run on another stream
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(g.stream);
-        (void)hipFree(buf);
-        if (e == hipErrorInvalidValue)
-            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
-                                            "slices)", g.nx, g.ny, g.nz);
-        return hip_fail(e, "vr_bake_quantile(k_bake_quant)");
-    }
-    g.qstats = buf;
-    g.qplane = plane;
-    g.qsy = psy;
-    g.qsz = psz;
-    g.volume_epoch++;
-    return VR_OK;
-}
-
-int vr_release_quantile(void) {
-    release_quantile();
-    return VR_OK;
-}
-
+int vr_bake_quantile(void) { return bake_query(*record_query(VR_QUERY_QUANTILE)); }
+int vr_release_quantile(void) { return release_query(VR_QUERY_QUANTILE); }
 int vr_quantile_info(const float **d_plane, uint64_t *plane_floats) {
-    if (d_plane) *d_plane = g.qstats;
-    if (plane_floats) *plane_floats = g.qplane;
-    return VR_OK;
+    return query_info(VR_QUERY_QUANTILE, d_plane, plane_floats);
 }
 
 // ---------------- distribution-distance query (method 12) ----
 
 int vr_set_query_target(const float *h, int n, int metric, int similarity) {
     if (!h) {  // clear
-        release_distance();
+        release_planes(query_plane(VR_QUERY_DISTANCE));
         g.dn = 0;
         g.dmetric = 0;
         g.dt = vr::DistTarget{};
@@ -2995,7 +2907,7 @@ int vr_set_query_target(const float *h, int n, int metric, int similarity) {
         return fail(VR_ERR_ARG, "unknown distance metric %d (VR_DIST_L1 / _EMD / _KS)", metric);
     for (int i = 0; i < n; i++)
         if (!std::isfinite(h[i])) return fail(VR_ERR_ARG, "target bin %d is not finite", i);
-    release_distance();  // a plane baked against another target
+    release_planes(query_plane(VR_QUERY_DISTANCE));  // a plane baked against another target
     vr::DistTarget t = {};
     std::memcpy(t.h, h, (size_t)n * sizeof(float));  // (h may be g.dt.h itself)
     t.similarity = similarity != 0;
@@ -3065,63 +2977,17 @@ int vr_set_query_target_region(int x0, int y0, int z0, int x1, int y1, int z1, i
     return vr_set_query_target(h, g.nb, metric, similarity);
 }
 
-int vr_bake_distance(void) {
-    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
-    if (g.dn == 0)
-        return fail(VR_ERR_STATE, "no query target set (vr_set_query_target / "
-                                  "vr_set_query_target_region)");
-    if (g.dn != g.nb)
-        return fail(VR_ERR_STATE, "a target of %d bins is set, the resident records have %d bins",
-                    g.dn, g.nb);
-    if (g.dstats) return VR_OK;  // baked against this target: any change drops the plane
-    vr::Params P;
-    std::memset(&P, 0, sizeof P);
-    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
-    P.sy = g.sy; P.sz = g.sz;
-    P.nb = g.nb;
-    uint64_t psy = 0, psz = 0;
-    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
-    const uint64_t plane = psz * (uint64_t)g.nz;
-    float *buf = nullptr;
-    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
-    // (the plane's padding is read with weight 0: it must hold finite floats)
-    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
-    if (e == hipSuccess)
-        e = vr::launch_bake_dist(g.vol, is_f16(), P, g.dt, g.dmetric, buf, psy, psz, g.stream);
-    // synchronous, like vr_bake_stats: a later frame may run on another stream
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(g.stream);
-        (void)hipFree(buf);
-        if (e == hipErrorInvalidValue)
-            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
-                                            "slices)", g.nx, g.ny, g.nz);
-        return hip_fail(e, "vr_bake_distance(k_bake_dist)");
-    }
-    g.dstats = buf;
-    g.dplane = plane;
-    g.dsy = psy;
-    g.dsz = psz;
-    g.volume_epoch++;
-    return VR_OK;
-}
-
-int vr_release_distance(void) {
-    release_distance();
-    return VR_OK;
-}
-
+int vr_bake_distance(void) { return bake_query(*record_query(VR_QUERY_DISTANCE)); }
+int vr_release_distance(void) { return release_query(VR_QUERY_DISTANCE); }
 int vr_distance_info(const float **d_plane, uint64_t *plane_floats) {
-    if (d_plane) *d_plane = g.dstats;
-    if (plane_floats) *plane_floats = g.dplane;
-    return VR_OK;
+    return query_info(VR_QUERY_DISTANCE, d_plane, plane_floats);
 }
 
 // ---------------- level-crossing query (method 13) ----------
 
 int vr_set_crossing_weights(const float *w, int n) {
     if (!w) {  // clear
-        release_crossing();
+        release_planes(query_plane(VR_QUERY_CROSSING));
         g.xn = 0;
         g.xw = vr::BinWeights{};
         return VR_OK;
@@ -3130,7 +2996,7 @@ int vr_set_crossing_weights(const float *w, int n) {
         return fail(VR_ERR_UNSUPPORTED, "%d crossing weights (supported: 1,2,4,8,16,32)", n);
     for (int i = 0; i < n; i++)
         if (!std::isfinite(w[i])) return fail(VR_ERR_ARG, "crossing weight %d is not finite", i);
-    release_crossing();  // a plane baked with other weights
+    release_planes(query_plane(VR_QUERY_CROSSING));  // a plane baked with other weights
     vr::BinWeights t = {};
     std::memcpy(t.w, w, (size_t)n * sizeof(float));  // (w may be g.xw.w itself)
     g.xw = t;
@@ -3150,73 +3016,22 @@ int vr_set_isovalue(float theta, int n) {
         return fail(VR_ERR_UNSUPPORTED, "%d crossing weights (supported: 1,2,4,8,16,32)", n);
     if (!std::isfinite(theta)) return fail(VR_ERR_ARG, "vr_set_isovalue: theta must be finite");
     float w[32];
-    const double h = (double)theta, dn = (double)n;
-    for (int i = 0; i < n; i++) {  // the part of [0, theta) inside bin i, in bin widths
-        const double a = (double)i / dn, b = std::min(h, ((double)i + 1.0) / dn);
-        w[i] = (float)(dn * std::max(0.0, b - a));
-    }
+    interval_weights(0.0f, theta, n, w);  // [0, theta)
     return vr_set_crossing_weights(w, n);
 }
 
-int vr_bake_crossing(void) {
-    if (!g.vol) return fail(VR_ERR_STATE, "no volume resident (initCuda / vr_init_* first)");
-    if (g.xn == 0)
-        return fail(VR_ERR_STATE, "no crossing weights set (vr_set_isovalue / "
-                                  "vr_set_crossing_weights)");
-    if (g.xn != g.nb)
-        return fail(VR_ERR_STATE, "%d crossing weights are set, the resident records have %d bins",
-                    g.xn, g.nb);
-    if (g.xstats) return VR_OK;  // baked with these weights: any change drops the plane
-    vr::Params P;
-    std::memset(&P, 0, sizeof P);
-    P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
-    P.sy = g.sy; P.sz = g.sz;
-    P.nb = g.nb;
-    uint64_t psy = 0, psz = 0;
-    vr::plane_pitches((uint32_t)g.nx, (uint32_t)g.ny, psy, psz);
-    const uint64_t plane = psz * (uint64_t)g.nz;
-    float *buf = nullptr;
-    VR_HIP(hipMalloc(&buf, (plane + 4) * sizeof(float)));
-    // (the plane's padding is fetched beside a row's last voxel: it must be there)
-    hipError_t e = hipMemsetAsync(buf, 0, (plane + 4) * sizeof(float), g.stream);
-    // the plane of F is method 10's statistic of the crossing weights: k_bake_lin
-    if (e == hipSuccess)
-        e = vr::launch_bake_lin(g.vol, is_f16(), P, g.xw, buf, psy, psz, g.stream);
-    // synchronous, like vr_bake_stats: a later frame may run on another stream
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(g.stream);
-        (void)hipFree(buf);
-        if (e == hipErrorInvalidValue)
-            return fail(VR_ERR_UNSUPPORTED, "baking a %d x %d x %d volume (at most 65535 rows and "
-                                            "slices)", g.nx, g.ny, g.nz);
-        return hip_fail(e, "vr_bake_crossing(k_bake_lin)");
-    }
-    g.xstats = buf;
-    g.xplane = plane;
-    g.xsy = psy;
-    g.xsz = psz;
-    g.volume_epoch++;
-    return VR_OK;
-}
-
-int vr_release_crossing(void) {
-    release_crossing();
-    return VR_OK;
-}
-
+int vr_bake_crossing(void) { return bake_query(*record_query(VR_QUERY_CROSSING)); }
+int vr_release_crossing(void) { return release_query(VR_QUERY_CROSSING); }
 int vr_crossing_info(const float **d_plane, uint64_t *plane_floats) {
-    if (d_plane) *d_plane = g.xstats;
-    if (plane_floats) *plane_floats = g.xplane;
-    return VR_OK;
+    return query_info(VR_QUERY_CROSSING, d_plane, plane_floats);
 }
 
 int vr_stats_info(const float **d_raw, uint64_t *raw_plane, const float **d_codec,
                   uint64_t *codec_plane) {
-    if (d_raw) *d_raw = g.stats;
-    if (raw_plane) *raw_plane = g.stats_plane;
-    if (d_codec) *d_codec = g.cstats;
-    if (codec_plane) *codec_plane = g.cstats_plane;
+    if (d_raw) *d_raw = g.stats.buf;
+    if (raw_plane) *raw_plane = g.stats.floats;
+    if (d_codec) *d_codec = g.cstats.buf;
+    if (codec_plane) *codec_plane = g.cstats.floats;
     return VR_OK;
 }
 

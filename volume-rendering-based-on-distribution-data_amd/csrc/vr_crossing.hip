@@ -122,27 +122,16 @@ __global__ __launch_bounds__(256) void k_march_cross_plane(const float *__restri
     if (P.tile_cost) record_tile_cost(P, tile, n);  // all lanes have reconverged here
 }
 
-template <typename T>
-static hipError_t march_cross_t(const T *vol, const Params &P, const BinWeights &W,
-                                uint32_t nslots, hipStream_t s) {
-    const dim3 grid(nslots), block(256);
-    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_march_cross<T, 1>), grid, block, lds, s, vol, P, W); break;
-    case 2: hipLaunchKernelGGL((k_march_cross<T, 2>), grid, block, lds, s, vol, P, W); break;
-    case 4: hipLaunchKernelGGL((k_march_cross<T, 4>), grid, block, lds, s, vol, P, W); break;
-    case 8: hipLaunchKernelGGL((k_march_cross<T, 8>), grid, block, lds, s, vol, P, W); break;
-    case 16: hipLaunchKernelGGL((k_march_cross<T, 16>), grid, block, lds, s, vol, P, W); break;
-    case 32: hipLaunchKernelGGL((k_march_cross<T, 32>), grid, block, lds, s, vol, P, W); break;
-    default: return hipErrorInvalidValue;  // no runtime-B instance
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_march_cross(const void *vol, bool half, const Params &P, const BinWeights &W,
                               uint32_t nslots, hipStream_t s) {
-    const hipError_t e = half ? march_cross_t(static_cast<const _Float16 *>(vol), P, W, nslots, s)
-                              : march_cross_t(static_cast<const float *>(vol), P, W, nslots, s);
+    const dim3 grid(nslots), block(256);
+    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
+    if (!with_records(vol, half, P.nb, [&](auto v, auto B) {
+            using T = ElemOf<decltype(v)>;
+            hipLaunchKernelGGL((k_march_cross<T, decltype(B)::value>), grid, block, lds, s, v, P, W);
+        }))
+        return hipErrorInvalidValue;  // no runtime-B instance
+    const hipError_t e = hipGetLastError();
     if (e == hipSuccess) note_kernel("k_march_cross", P.nb, 13);
     return e;
 }

@@ -53,76 +53,37 @@ __global__ __launch_bounds__(256) void k_bake_dist(const T *__restrict__ vol, Pa
     bake_lin_kernel<T, B>(vol, P, DistStat<METRIC>{H}, out, psy, psz);
 }
 
-template <typename T, int METRIC>
-static hipError_t march_dist_t(const T *vol, const Params &P, const DistTarget &H,
-                               uint32_t nslots, hipStream_t s) {
-    const dim3 grid(nslots), block(256);
-    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_march_dist<T, 1, METRIC>), grid, block, lds, s, vol, P, H); break;
-    case 2: hipLaunchKernelGGL((k_march_dist<T, 2, METRIC>), grid, block, lds, s, vol, P, H); break;
-    case 4: hipLaunchKernelGGL((k_march_dist<T, 4, METRIC>), grid, block, lds, s, vol, P, H); break;
-    case 8: hipLaunchKernelGGL((k_march_dist<T, 8, METRIC>), grid, block, lds, s, vol, P, H); break;
-    case 16: hipLaunchKernelGGL((k_march_dist<T, 16, METRIC>), grid, block, lds, s, vol, P, H); break;
-    case 32: hipLaunchKernelGGL((k_march_dist<T, 32, METRIC>), grid, block, lds, s, vol, P, H); break;
-    default: return hipErrorInvalidValue;  // no runtime-B instance
-    }
-    return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t march_dist_m(const T *vol, const Params &P, const DistTarget &H, int metric,
-                               uint32_t nslots, hipStream_t s) {
-    switch (metric) {
-    case 0: return march_dist_t<T, 0>(vol, P, H, nslots, s);
-    case 1: return march_dist_t<T, 1>(vol, P, H, nslots, s);
-    case 2: return march_dist_t<T, 2>(vol, P, H, nslots, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t launch_march_dist(const void *vol, bool half, const Params &P, const DistTarget &H,
                              int metric, uint32_t nslots, hipStream_t s) {
-    const hipError_t e =
-        half ? march_dist_m(static_cast<const _Float16 *>(vol), P, H, metric, nslots, s)
-             : march_dist_m(static_cast<const float *>(vol), P, H, metric, nslots, s);
+    const dim3 grid(nslots), block(256);
+    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
+    if (!with_value<0, 1, 2>(metric, [&](auto M) {
+            return with_records(vol, half, P.nb, [&](auto v, auto B) {
+                using T = ElemOf<decltype(v)>;
+                hipLaunchKernelGGL((k_march_dist<T, decltype(B)::value, decltype(M)::value>), grid,
+                                   block, lds, s, v, P, H);
+            });
+        }))
+        return hipErrorInvalidValue;  // no such metric, or no runtime-B instance
+    const hipError_t e = hipGetLastError();
     if (e == hipSuccess) note_kernel("k_march_dist", P.nb, 12);
     return e;
 }
 
-template <typename T, int METRIC>
-static hipError_t bake_dist_t(const T *vol, const Params &P, const DistTarget &H, float *out,
-                              uint64_t psy, uint64_t psz, hipStream_t s) {
+hipError_t launch_bake_dist(const void *vol, bool half, const Params &P, const DistTarget &H,
+                            int metric, float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
     dim3 grid;
     const dim3 block(256);
     if (!bake_lin_grid(P, grid)) return hipErrorInvalidValue;
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_bake_dist<T, 1, METRIC>), grid, block, 0, s, vol, P, H, out, psy, psz); break;
-    case 2: hipLaunchKernelGGL((k_bake_dist<T, 2, METRIC>), grid, block, 0, s, vol, P, H, out, psy, psz); break;
-    case 4: hipLaunchKernelGGL((k_bake_dist<T, 4, METRIC>), grid, block, 0, s, vol, P, H, out, psy, psz); break;
-    case 8: hipLaunchKernelGGL((k_bake_dist<T, 8, METRIC>), grid, block, 0, s, vol, P, H, out, psy, psz); break;
-    case 16: hipLaunchKernelGGL((k_bake_dist<T, 16, METRIC>), grid, block, 0, s, vol, P, H, out, psy, psz); break;
-    case 32: hipLaunchKernelGGL((k_bake_dist<T, 32, METRIC>), grid, block, 0, s, vol, P, H, out, psy, psz); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (!with_value<0, 1, 2>(metric, [&](auto M) {
+            return with_records(vol, half, P.nb, [&](auto v, auto B) {
+                using T = ElemOf<decltype(v)>;
+                hipLaunchKernelGGL((k_bake_dist<T, decltype(B)::value, decltype(M)::value>), grid,
+                                   block, 0, s, v, P, H, out, psy, psz);
+            });
+        }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t bake_dist_m(const T *vol, const Params &P, const DistTarget &H, int metric,
-                              float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
-    switch (metric) {
-    case 0: return bake_dist_t<T, 0>(vol, P, H, out, psy, psz, s);
-    case 1: return bake_dist_t<T, 1>(vol, P, H, out, psy, psz, s);
-    case 2: return bake_dist_t<T, 2>(vol, P, H, out, psy, psz, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_bake_dist(const void *vol, bool half, const Params &P, const DistTarget &H,
-                            int metric, float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
-    return half ? bake_dist_m(static_cast<const _Float16 *>(vol), P, H, metric, out, psy, psz, s)
-                : bake_dist_m(static_cast<const float *>(vol), P, H, metric, out, psy, psz, s);
 }
 
 }  // namespace vr

@@ -57,62 +57,37 @@ __global__ __launch_bounds__(256) void k_bake_quant(const T *__restrict__ vol, P
     bake_lin_kernel<T, B>(vol, P, QuantStat<SPREAD>{Q.q_lo, Q.q_hi}, out, psy, psz);
 }
 
-template <typename T, bool SPREAD>
-static hipError_t march_quant_t(const T *vol, const Params &P, const QuantArgs &Q,
-                                uint32_t nslots, hipStream_t s) {
-    const dim3 grid(nslots), block(256);
-    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_march_quant<T, 1, SPREAD>), grid, block, lds, s, vol, P, Q); break;
-    case 2: hipLaunchKernelGGL((k_march_quant<T, 2, SPREAD>), grid, block, lds, s, vol, P, Q); break;
-    case 4: hipLaunchKernelGGL((k_march_quant<T, 4, SPREAD>), grid, block, lds, s, vol, P, Q); break;
-    case 8: hipLaunchKernelGGL((k_march_quant<T, 8, SPREAD>), grid, block, lds, s, vol, P, Q); break;
-    case 16: hipLaunchKernelGGL((k_march_quant<T, 16, SPREAD>), grid, block, lds, s, vol, P, Q); break;
-    case 32: hipLaunchKernelGGL((k_march_quant<T, 32, SPREAD>), grid, block, lds, s, vol, P, Q); break;
-    default: return hipErrorInvalidValue;  // no runtime-B instance
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_march_quant(const void *vol, bool half, const Params &P, const QuantArgs &Q,
                               bool spread, uint32_t nslots, hipStream_t s) {
-    const _Float16 *h = static_cast<const _Float16 *>(vol);
-    const float *f = static_cast<const float *>(vol);
-    const hipError_t e =
-        half ? (spread ? march_quant_t<_Float16, true>(h, P, Q, nslots, s)
-                       : march_quant_t<_Float16, false>(h, P, Q, nslots, s))
-             : (spread ? march_quant_t<float, true>(f, P, Q, nslots, s)
-                       : march_quant_t<float, false>(f, P, Q, nslots, s));
+    const dim3 grid(nslots), block(256);
+    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
+    if (!with_value<0, 1>(spread, [&](auto SP) {
+            return with_records(vol, half, P.nb, [&](auto v, auto B) {
+                using T = ElemOf<decltype(v)>;
+                hipLaunchKernelGGL((k_march_quant<T, decltype(B)::value, decltype(SP)::value != 0>),
+                                   grid, block, lds, s, v, P, Q);
+            });
+        }))
+        return hipErrorInvalidValue;  // no runtime-B instance
+    const hipError_t e = hipGetLastError();
     if (e == hipSuccess) note_kernel("k_march_quant", P.nb, 11);
     return e;
 }
 
-template <typename T, bool SPREAD>
-static hipError_t bake_quant_t(const T *vol, const Params &P, const QuantArgs &Q, float *out,
-                               uint64_t psy, uint64_t psz, hipStream_t s) {
+hipError_t launch_bake_quant(const void *vol, bool half, const Params &P, const QuantArgs &Q,
+                             bool spread, float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
     dim3 grid;
     const dim3 block(256);
     if (!bake_lin_grid(P, grid)) return hipErrorInvalidValue;
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_bake_quant<T, 1, SPREAD>), grid, block, 0, s, vol, P, Q, out, psy, psz); break;
-    case 2: hipLaunchKernelGGL((k_bake_quant<T, 2, SPREAD>), grid, block, 0, s, vol, P, Q, out, psy, psz); break;
-    case 4: hipLaunchKernelGGL((k_bake_quant<T, 4, SPREAD>), grid, block, 0, s, vol, P, Q, out, psy, psz); break;
-    case 8: hipLaunchKernelGGL((k_bake_quant<T, 8, SPREAD>), grid, block, 0, s, vol, P, Q, out, psy, psz); break;
-    case 16: hipLaunchKernelGGL((k_bake_quant<T, 16, SPREAD>), grid, block, 0, s, vol, P, Q, out, psy, psz); break;
-    case 32: hipLaunchKernelGGL((k_bake_quant<T, 32, SPREAD>), grid, block, 0, s, vol, P, Q, out, psy, psz); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (!with_value<0, 1>(spread, [&](auto SP) {
+            return with_records(vol, half, P.nb, [&](auto v, auto B) {
+                using T = ElemOf<decltype(v)>;
+                hipLaunchKernelGGL((k_bake_quant<T, decltype(B)::value, decltype(SP)::value != 0>),
+                                   grid, block, 0, s, v, P, Q, out, psy, psz);
+            });
+        }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
-}
-
-hipError_t launch_bake_quant(const void *vol, bool half, const Params &P, const QuantArgs &Q,
-                             bool spread, float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
-    const _Float16 *h = static_cast<const _Float16 *>(vol);
-    const float *f = static_cast<const float *>(vol);
-    return half ? (spread ? bake_quant_t<_Float16, true>(h, P, Q, out, psy, psz, s)
-                          : bake_quant_t<_Float16, false>(h, P, Q, out, psy, psz, s))
-                : (spread ? bake_quant_t<float, true>(f, P, Q, out, psy, psz, s)
-                          : bake_quant_t<float, false>(f, P, Q, out, psy, psz, s));
 }
 
 }  // namespace vr

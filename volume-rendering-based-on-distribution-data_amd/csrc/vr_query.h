@@ -224,6 +224,37 @@ __device__ __forceinline__ void bake_lin_kernel(const T *vol, const Params &P, c
     put_plane(out, x, blockIdx.y, blockIdx.z, psy, psz, st(r));
 }
 
+// Host-side dispatch of the launchers, from a runtime value to the template
+// argument of a compiled instance: f(std::integral_constant<int, V>{}) for the V
+// among Vs that v equals, and what f returns (launched); false, nothing called:
+// no instance for v.
+template <int... Vs, typename F>
+inline bool with_value(int v, F &&f) {
+    return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
+}
+
+// the bin counts the query kernels are compiled for (no runtime-B instance):
+// f(std::integral_constant<int, B>{})
+template <typename F>
+inline bool with_bins(int nb, F &&f) {
+    return with_value<1, 2, 4, 8, 16, 32>(nb, [&](auto B) {
+        f(B);
+        return true;
+    });
+}
+
+// ... and the records' element type with them: f(v, B), v the volume as
+// const float * or const _Float16 * (ElemOf<decltype(v)>: that type)
+template <typename F>
+inline bool with_records(const void *vol, bool half, int nb, F &&f) {
+    return with_bins(nb, [&](auto B) {
+        if (half) f(static_cast<const _Float16 *>(vol), B);
+        else f(static_cast<const float *>(vol), B);
+    });
+}
+template <typename P>
+using ElemOf = std::remove_cv_t<std::remove_pointer_t<P>>;
+
 // the grid of a bake launch; false: more rows or slices than a grid takes
 inline bool bake_lin_grid(const Params &P, dim3 &grid) {
     if (P.nx <= 0 || P.ny <= 0 || P.nz <= 0 || P.ny > 65535 || P.nz > 65535) return false;

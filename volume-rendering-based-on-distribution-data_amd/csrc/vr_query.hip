@@ -52,53 +52,32 @@ __global__ __launch_bounds__(256) void k_bake_lin(const T *__restrict__ vol, Par
     bake_lin_kernel<T, B>(vol, P, LinStat{W}, out, psy, psz);
 }
 
-template <typename T>
-static hipError_t march_lin_t(const T *vol, const Params &P, const BinWeights &W, uint32_t nslots,
-                              hipStream_t s) {
-    const dim3 grid(nslots), block(256);
-    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_march_lin<T, 1>), grid, block, lds, s, vol, P, W); break;
-    case 2: hipLaunchKernelGGL((k_march_lin<T, 2>), grid, block, lds, s, vol, P, W); break;
-    case 4: hipLaunchKernelGGL((k_march_lin<T, 4>), grid, block, lds, s, vol, P, W); break;
-    case 8: hipLaunchKernelGGL((k_march_lin<T, 8>), grid, block, lds, s, vol, P, W); break;
-    case 16: hipLaunchKernelGGL((k_march_lin<T, 16>), grid, block, lds, s, vol, P, W); break;
-    case 32: hipLaunchKernelGGL((k_march_lin<T, 32>), grid, block, lds, s, vol, P, W); break;
-    default: return hipErrorInvalidValue;  // no runtime-B instance
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_march_lin(const void *vol, bool half, const Params &P, const BinWeights &W,
                             uint32_t nslots, hipStream_t s) {
-    const hipError_t e = half ? march_lin_t(static_cast<const _Float16 *>(vol), P, W, nslots, s)
-                              : march_lin_t(static_cast<const float *>(vol), P, W, nslots, s);
+    const dim3 grid(nslots), block(256);
+    const size_t lds = occupancy_lds(P);  // VR_WG_PER_CU; the kernel itself uses no LDS
+    if (!with_records(vol, half, P.nb, [&](auto v, auto B) {
+            using T = ElemOf<decltype(v)>;
+            hipLaunchKernelGGL((k_march_lin<T, decltype(B)::value>), grid, block, lds, s, v, P, W);
+        }))
+        return hipErrorInvalidValue;  // no runtime-B instance
+    const hipError_t e = hipGetLastError();
     if (e == hipSuccess) note_kernel("k_march_lin", P.nb, 10);
     return e;
 }
 
-template <typename T>
-static hipError_t bake_lin_t(const T *vol, const Params &P, const BinWeights &W, float *out,
-                             uint64_t psy, uint64_t psz, hipStream_t s) {
+hipError_t launch_bake_lin(const void *vol, bool half, const Params &P, const BinWeights &W,
+                           float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
     dim3 grid;
     const dim3 block(256);
     if (!bake_lin_grid(P, grid)) return hipErrorInvalidValue;
-    switch (P.nb) {
-    case 1: hipLaunchKernelGGL((k_bake_lin<T, 1>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
-    case 2: hipLaunchKernelGGL((k_bake_lin<T, 2>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
-    case 4: hipLaunchKernelGGL((k_bake_lin<T, 4>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
-    case 8: hipLaunchKernelGGL((k_bake_lin<T, 8>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
-    case 16: hipLaunchKernelGGL((k_bake_lin<T, 16>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
-    case 32: hipLaunchKernelGGL((k_bake_lin<T, 32>), grid, block, 0, s, vol, P, W, out, psy, psz); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (!with_records(vol, half, P.nb, [&](auto v, auto B) {
+            using T = ElemOf<decltype(v)>;
+            hipLaunchKernelGGL((k_bake_lin<T, decltype(B)::value>), grid, block, 0, s, v, P, W, out,
+                               psy, psz);
+        }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
-}
-
-hipError_t launch_bake_lin(const void *vol, bool half, const Params &P, const BinWeights &W,
-                           float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
-    return half ? bake_lin_t(static_cast<const _Float16 *>(vol), P, W, out, psy, psz, s)
-                : bake_lin_t(static_cast<const float *>(vol), P, W, out, psy, psz, s);
 }
 
 }  // namespace vr
