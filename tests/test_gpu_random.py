@@ -8,6 +8,7 @@ from their seed (printed in the failure message)."""
 import numpy as np
 import pytest
 
+from random_cases import draw_view
 from test_gpu_parity import assert_parity, codec_render, gpu_render
 
 pytestmark = pytest.mark.gpu
@@ -20,20 +21,10 @@ PATHS = [{}, {}, {"VR_PATH": "0"}, {"VR_PATH": "1"}, {"VR_PATH": "1", "VR_BOX_MA
 
 
 def draw_camera(pkg, rng):
-    kind = rng.integers(0, 4)
-    if kind == 0:  # row-aligned (runSingleTest family), shifted / zoomed
-        return pkg.camera.display_inv_view(
-            (0.0, 0.0), (rng.uniform(-0.6, 0.6), rng.uniform(-0.6, 0.6), -rng.uniform(1.2, 6.0)))
-    if kind == 1:  # axis-aligned quarter turns
-        rx, ry = (float(rng.choice([0, 90, 180, 270])) for _ in range(2))
-        return pkg.camera.display_inv_view((rx, ry), (0.0, 0.0, -rng.uniform(2.5, 5.0)))
-    if kind == 2:  # eye inside the volume
-        return pkg.camera.display_inv_view(
-            (rng.uniform(-180, 180), rng.uniform(-180, 180)),
-            (rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5)))
-    return pkg.camera.display_inv_view(
-        (rng.uniform(-180, 180), rng.uniform(-180, 180)),
-        (rng.uniform(-0.4, 0.4), rng.uniform(-0.4, 0.4), -rng.uniform(1.5, 6.0)))
+    """row-aligned, quarter turns, eye inside the volume or oblique: the angles and
+    translations are random_cases.draw_view's"""
+    _, rotation, translation = draw_view(rng)
+    return pkg.camera.display_inv_view(rotation, translation)
 
 
 def draw_params(rng):
