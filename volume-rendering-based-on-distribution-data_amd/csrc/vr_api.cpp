@@ -73,27 +73,26 @@ struct State {
     // chain holds a front and a back z-range)
     Gmm gmm_parked[2];
     int gmm_slot = 0;
-    // baked GMM statistics (vr_bake_gmm_stats, vr_gmm.hip k_bake_gmm): two
-    // whole-volume planes of `plane` floats, the mean and 16 x variance of every
-    // voxel of an nx x ny x nz volume, filled slab by slab (slice[z]: baked);
-    // tied to no slot and to no resident records
+    // A baked set of GMM planes (vr_bake_gmm_*, vr_gmm.hip k_bake_gmm*): whole-volume
+    // planes of `plane` floats, a statistic of every voxel of an nx x ny x nz
+    // volume, filled slab by slab (slice[z]: baked); tied to no slot and to no
+    // resident records
     struct GmmStats {
         float *buf = nullptr;
         int nx = 0, ny = 0, nz = 0;
         uint64_t plane = 0, sy = 0, sz = 0;  // plane_pitches
         std::vector<unsigned char> slice;
         int nbaked = 0;
-    } gstats;
-    // range probability of GMM volumes (method 10): the
-    // bounds (host state) and the plane vr_bake_gmm_range made of them -- one
-    // plane in gstats' layout, with slice flags of its own, independent of gstats
+    };
+    // The three sets (kGmmPlaneSets below, one row each), each with
+    // slice flags of its own and independent of the others: the mean and 16 x
+    // variance (two planes), the range probability (method 10, section 18: one plane
+    // made of the bounds grq) and the quantile (method 11, section 19: one plane made
+    // of the quantile state qq, qmode below)
+    enum { kGmmStats, kGmmRange, kGmmQuant, kGmmSets };
+    GmmStats gplanes[kGmmSets];
     vr::GmmRange grq = {};
     bool grq_set = false;
-    GmmStats grange;
-    // quantile of GMM volumes (method 11): the plane
-    // vr_bake_gmm_quantile made of the quantile state below (qq, qmode) -- a third
-    // plane set of one plane, independent of gstats and grange
-    GmmStats gquant;
     // A baked set of planes of one float per voxel in x-row bricks (plane_pitches),
     // one allocation: `floats` floats a plane, pitches sy / sz; buf nullptr = not
     // baked
@@ -1676,9 +1675,9 @@ namespace {
 static_assert(vr::kPlanTileRays == vr::kTileW * vr::kTileH && vr::kPlanBoxMax == vr::kBoxMax,
               "vr_plan.h repeats vr_device.h's tile size and box capacity");
 
-// What plan_march() reads of a frame of methods 1/2/3/7 over the resident record
-// volume (P: fill_params' result, with the clip rectangle applied).
-vr::PlanIn plan_input(const vr_render_desc *d, const vr::Params &P, bool count) {
+// What plan_march() reads of any frame: the view, the image with the rendered
+// rectangle (P: with the clip applied), the tile list and the tuning knobs.
+vr::PlanIn plan_frame(const vr_render_desc *d, const vr::Params &P) {
     vr::PlanIn in = {};
     in.m0 = d->inv_view[0];
     in.m4 = d->inv_view[4];
@@ -1689,6 +1688,14 @@ vr::PlanIn plan_input(const vr_render_desc *d, const vr::Params &P, bool count) 
     in.CH = P.CH;
     in.tile_list = d->d_tile_list != nullptr;
     in.n_tiles = d->n_tiles;
+    in.tuning = vr::tuning;
+    return in;
+}
+
+// ... and of a frame of methods 1/2/3/7 over the resident record volume (P:
+// fill_params' result).
+vr::PlanIn plan_input(const vr_render_desc *d, const vr::Params &P, bool count) {
+    vr::PlanIn in = plan_frame(d, P);
     in.method = d->query_method;
     // (methods 4/5/6 come here only for their baked planes: the codec volume's)
     const bool codec = d->query_method >= 4 && d->query_method <= 6;
@@ -1705,7 +1712,6 @@ vr::PlanIn plan_input(const vr_render_desc *d, const vr::Params &P, bool count) 
     in.m7y = P.m7y;
     in.m7z = P.m7z;
     in.count = count;
-    in.tuning = vr::tuning;
     return in;
 }
 
@@ -1727,38 +1733,30 @@ void apply_plan(const vr::MarchPlan &pl, vr::Params &P) {
     P.wg_per_cu = pl.wg_per_cu;
 }
 
-// a frame from a plane of one float per voxel baked from the records (the
-// weighted plane, the quantile plane, the distance plane) in x-row bricks of
-// pitches psy / psz
-int launch_record_plane(const vr_render_desc *desc, vr::Params &P, uint32_t nslots,
-                        const float *plane, uint64_t psy, uint64_t psz, hipError_t &e) {
-    vr::PlanIn in = {};
-    in.m0 = desc->inv_view[0];
-    in.m4 = desc->inv_view[4];
-    in.m8 = desc->inv_view[8];
-    in.W = desc->width;
-    in.H = desc->height;
-    in.CW = P.CW;
-    in.CH = P.CH;
-    in.tile_list = desc->d_tile_list != nullptr;
-    in.n_tiles = desc->n_tiles;
-    in.method = 1;  // any plane statistic: the plan of a baked frame reads no more of it
+// A frame from a baked plane of one float per voxel of P's grid, in x-row bricks
+// of pitches psy / psz: the weighted, quantile and distance planes of the records
+// and the planes of a GMM volume (vr_render_gmm_baked).  The plan's plane march on
+// the bricks themselves -- such a plane has no layout copies.
+int launch_plane_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots,
+                       const float *plane, uint64_t psy, uint64_t psz, hipError_t &e) {
+    vr::PlanIn in = plan_frame(desc, P);
+    // any plane statistic (a variance plane too: the plan of a baked frame tells
+    // methods 1 and 2 apart nowhere)
+    in.method = 1;
     in.nb = 1;
-    in.nx = g.nx;
-    in.ny = g.ny;
-    in.nz = g.nz;
+    in.nx = P.nx;
+    in.ny = P.ny;
+    in.nz = P.nz;
     in.owned = false;
     in.f16 = false;
     in.baked = true;
     in.plane_sy = psy;
     in.plane_sz = psz;
     in.count = false;
-    // the x-row bricks only: no layout copies of such a plane
     in.denied = vr::kLayoutAxis | vr::kLayoutBrick | vr::kLayoutPlane;
-    in.tuning = vr::tuning;
     const vr::MarchPlan pl = vr::plan_march(in);
     if (pl.layout != vr::kLayoutNone || pl.method > 0)
-        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of a baked query plane");
+        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of a baked plane");
     apply_plan(pl, P);
     P.nb = 1;
     P.sy = psy;
@@ -1770,7 +1768,7 @@ int launch_record_plane(const vr_render_desc *desc, vr::Params &P, uint32_t nslo
 // The march of a frame of record query q (check_method has passed).  Per step:
 // q's kernel on the x rows of the records, whatever the view -- no plan, no layout
 // copy.  With q's baked plane resident (vr_bake_*): the plane march plan_march
-// names for one float per voxel in x-row bricks, the route of vr_render_gmm_baked
+// names for one float per voxel in x-row bricks (launch_plane_frame)
 // -- the same eight floats into the same filter, so the same frame bit for bit.
 // Method 13 combines its eight corners where the others blend them: its plane of
 // F goes to k_march_cross_plane, the one-lane march for every view, no plan.
@@ -1781,7 +1779,7 @@ int launch_query(const RecordQuery &q, const vr_render_desc *desc, vr::Params &P
         e = q.march(P, nslots);
         return VR_OK;
     }
-    if (!q.cross_plane) return launch_record_plane(desc, P, nslots, pl.buf, pl.sy, pl.sz, e);
+    if (!q.cross_plane) return launch_plane_frame(desc, P, nslots, pl.buf, pl.sy, pl.sz, e);
     P.nb = 1;
     P.sy = pl.sy;
     P.sz = pl.sz;
@@ -2019,19 +2017,18 @@ void release_all_gmm() {
     g.gmm_slot = 0;
 }
 
-// baked GMM planes: the mean / variance pair (vr_release_gmm_stats) or the range
-// plane (vr_release_gmm_range, any change of the range) or the quantile plane
-// (vr_release_gmm_quantile, any set or clear of the quantile); freeCudaBuffers: all
-void release_gmm_planes(State::GmmStats &b) {
+// Frees a baked set of GMM planes: vr_release_gmm_*; the range plane on any change
+// of the range, the quantile plane on any set or clear of the quantile;
+// freeCudaBuffers: all
+int release_gmm_set(int set) {
+    State::GmmStats &b = g.gplanes[set];
     if (b.buf) {
         (void)hipFree(b.buf);
         g.volume_epoch++;  // a tile order learned on these planes is not reused
     }
     b = State::GmmStats{};
+    return VR_OK;
 }
-void release_gmm_stats() { release_gmm_planes(g.gstats); }
-void release_gmm_range() { release_gmm_planes(g.grange); }
-void release_gmm_quantile() { release_gmm_planes(g.gquant); }
 
 int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
     if (K != 8 && K != 16 && K != 32)
@@ -2049,6 +2046,76 @@ int check_gmm_shape(vr_extent dims, int K, int z_base, int nzs) {
     return VR_OK;
 }
 
+bool gmm_f16() { return g.gmm.dtype == VR_DTYPE_F16; }
+
+// The statistics of a GMM volume: the plane sets g.gplanes and the queryMethods
+// that read them (vr_gmm.hip holds the kernels, one march and one bake body for
+// all).  What differs between them on the host, one row each, in the order of
+// State::kGmmStats ...; everything else -- the checks, the planes' life, the frame
+// launches -- is written once below.
+struct GmmPlaneSet {
+    uint64_t nplanes;
+    const char *planes;           // the set, in messages
+    const char *bake, *release;   // its entry points and its bake kernel, in messages
+    const char *bake_kernel;
+    // the host state a bake or a per-step frame needs set (nullptr: none), and what
+    // sets it, in messages.  (Not a `[] { ... }`: the compiler gives the n-th lambda
+    // of one signature in each table of this file one name, and so one body.)
+    bool (*ready)(const State &s);
+    const char *state, *setters;
+    // the per-step march and the bake of the selected slot's resident slices
+    hipError_t (*march)(int method, const vr::Params &P, uint32_t nblocks);
+    hipError_t (*bake_launch)(float *out, uint64_t plane, uint64_t psy, uint64_t psz);
+};
+
+const GmmPlaneSet kGmmPlaneSets[State::kGmmSets] = {
+    {2, "planes", "vr_bake_gmm_stats", "vr_release_gmm_stats", "launch(k_bake_gmm)", nullptr,
+     nullptr, nullptr,
+     [](int method, const vr::Params &P, uint32_t nblocks) {
+         return vr::launch_march_gmm(g.gmm.K, method, gmm_f16(), P, nblocks, false, g.stream);
+     },
+     [](float *out, uint64_t plane, uint64_t psy, uint64_t psz) {
+         const State::Gmm &v = g.gmm;
+         return vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs, out,
+                                    plane, psy, psz, g.stream);
+     }},
+    {1, "range plane", "vr_bake_gmm_range", "vr_release_gmm_range", "launch(k_bake_gmm_range)",
+     [](const State &s) { return s.grq_set; }, "range", "vr_set_gmm_range",
+     [](int, const vr::Params &P, uint32_t nblocks) {
+         return vr::launch_march_gmm_range(g.gmm.K, gmm_f16(), P, g.grq, nblocks, g.stream);
+     },
+     [](float *out, uint64_t, uint64_t psy, uint64_t psz) {
+         const State::Gmm &v = g.gmm;
+         return vr::launch_bake_gmm_range(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
+                                          g.grq, out, psy, psz, g.stream);
+     }},
+    {1, "quantile plane", "vr_bake_gmm_quantile", "vr_release_gmm_quantile",
+     "launch(k_bake_gmm_quant)", [](const State &s) { return s.qmode != 0; }, "quantile",
+     "vr_set_quantile / vr_set_quantile_spread",
+     [](int, const vr::Params &P, uint32_t nblocks) {
+         return vr::launch_march_gmm_quant(g.gmm.K, gmm_f16(), P, g.qq, g.qmode == 2, nblocks,
+                                           g.stream);
+     },
+     [](float *out, uint64_t, uint64_t psy, uint64_t psz) {
+         const State::Gmm &v = g.gmm;
+         return vr::launch_bake_gmm_quant(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
+                                          g.qq, g.qmode == 2, out, psy, psz, g.stream);
+     }},
+};
+
+// the set queryMethod m reads; -1: none.  (Method 13 has no per-step GMM march: it
+// reads the range plane, as the plane of F = P(v < theta), in vr_render_gmm_baked.)
+int gmm_plane_set(int m) {
+    switch (m) {
+    case 1:
+    case 2: return State::kGmmStats;
+    case VR_QUERY_WEIGHTED:
+    case VR_QUERY_CROSSING: return State::kGmmRange;
+    case VR_QUERY_QUANTILE: return State::kGmmQuant;
+    default: return -1;
+    }
+}
+
 // Parameters of a GMM launch: the reference's ray / transfer / composite
 // inputs from the descriptor, the resident slices, and the slab.
 // count: a footprint count (no instance of the range probability or the quantile
@@ -2057,19 +2124,16 @@ int fill_gmm_params(const vr_render_desc *d, const vr_gmm_slab *slab, vr::Params
                     uint32_t &nblocks, bool count) {
     if (!d) return fail(VR_ERR_ARG, "null render descriptor");
     if (!g.gmm.wm) return fail(VR_ERR_STATE, "no GMM volume resident (vr_init_gmm / vr_synthesize_gmm)");
-    if (d->query_method == VR_QUERY_WEIGHTED && !count) {
-        if (!g.grq_set)
-            return fail(VR_ERR_STATE, "queryMethod 10 on a GMM volume needs a range (vr_set_gmm_range)");
-    } else if (d->query_method == VR_QUERY_QUANTILE && !count) {
-        if (g.qmode == 0)
-            return fail(VR_ERR_STATE, "queryMethod 11 on a GMM volume needs a quantile "
-                                      "(vr_set_quantile / vr_set_quantile_spread)");
-    } else if (d->query_method != 1 && d->query_method != 2) {
+    const int set = d->query_method == VR_QUERY_CROSSING ? -1 : gmm_plane_set(d->query_method);
+    if (set < 0 || (count && set != State::kGmmStats))
         return fail(VR_ERR_UNSUPPORTED, count
                     ? "GMM footprint counts support queryMethod 1 (mean) and 2 (variance)"
                     : "GMM volumes support queryMethod 1 (mean), 2 (variance), 10 (range "
                       "probability) and 11 (quantile)");
-    }
+    const GmmPlaneSet &ps = kGmmPlaneSets[set];
+    if (ps.ready && !ps.ready(g))
+        return fail(VR_ERR_STATE, "queryMethod %d on a GMM volume needs a %s (%s)",
+                    d->query_method, ps.state, ps.setters);
     if (!d->d_output) return fail(VR_ERR_ARG, "d_output is null");
     if (d->width == 0 || d->height == 0) return fail(VR_ERR_ARG, "empty image");
     if ((uint64_t)d->width * d->height > 0xFFFFFFFFull) return fail(VR_ERR_ARG, "image too large");
@@ -2164,8 +2228,6 @@ int fill_gmm_params(const vr_render_desc *d, const vr_gmm_slab *slab, vr::Params
     }
     return VR_OK;
 }
-
-bool gmm_f16() { return g.gmm.dtype == VR_DTYPE_F16; }
 
 // the widest loads k_march_gmm_h makes of a lane's chunk (vr_gmm.hip gmm_gather)
 constexpr size_t kGmmHalfAlignWm = 16, kGmmHalfAlignSigma = 8;
@@ -2354,16 +2416,8 @@ int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
     // (a caller zeroing it on another stream raced the launch)
     hipError_t e = slab ? hipMemsetAsync(slab->d_n_rays_out, 0, sizeof(uint32_t), g.stream)
                         : hipSuccess;
-    if (e == hipSuccess) {
-        if (desc->query_method == VR_QUERY_WEIGHTED)
-            e = vr::launch_march_gmm_range(g.gmm.K, gmm_f16(), P, g.grq, nblocks, g.stream);
-        else if (desc->query_method == VR_QUERY_QUANTILE)
-            e = vr::launch_march_gmm_quant(g.gmm.K, gmm_f16(), P, g.qq, g.qmode == 2, nblocks,
-                                           g.stream);
-        else
-            e = vr::launch_march_gmm(g.gmm.K, desc->query_method, gmm_f16(), P, nblocks, false,
-                                     g.stream);
-    }
+    if (e == hipSuccess)
+        e = kGmmPlaneSets[gmm_plane_set(desc->query_method)].march(desc->query_method, P, nblocks);
     if (e != hipSuccess) return hip_fail(e, gmm_f16() ? "launch(k_march_gmm_h)" : "launch(k_march_gmm)");
     return VR_OK;
 }
@@ -2400,30 +2454,22 @@ int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_sla
     return (int64_t)u;
 }
 
-// The selected slot's resident slices decoded once per voxel into the
-// whole-volume planes (k_bake_gmm, queued on the library stream).  The first
-// call allocates and zeroes the planes; if it fails, nothing has changed.
 }  // extern "C"
 
 namespace {
 
-// vr_bake_gmm_stats (b = gstats, two planes), vr_bake_gmm_range (b = grange, one) and
-// vr_bake_gmm_quantile (b = gquant, one)
-enum GmmBake { kBakeStats, kBakeRange, kBakeQuantile };
-int bake_gmm_planes(State::GmmStats &b, GmmBake kind) {
+// vr_bake_gmm_*: the selected slot's resident slices decoded once per voxel into the
+// set's whole-volume planes (its bake kernel, queued on the library stream).  The
+// first call allocates and zeroes the planes; if it fails, nothing has changed.
+int bake_gmm_planes(int set) {
+    const GmmPlaneSet &ps = kGmmPlaneSets[set];
+    State::GmmStats &b = g.gplanes[set];
     const State::Gmm &v = g.gmm;
-    const bool range = kind == kBakeRange, quant = kind == kBakeQuantile;
-    const uint64_t nplanes = kind == kBakeStats ? 2 : 1;
-    const char *fn = quant ? "vr_bake_gmm_quantile" : range ? "vr_bake_gmm_range" : "vr_bake_gmm_stats";
     if (!v.wm) return fail(VR_ERR_STATE, "no GMM volume resident (vr_init_gmm / vr_synthesize_gmm)");
-    if (range && !g.grq_set) return fail(VR_ERR_STATE, "no range set (vr_set_gmm_range)");
-    if (quant && g.qmode == 0)
-        return fail(VR_ERR_STATE, "no quantile set (vr_set_quantile / vr_set_quantile_spread)");
+    if (ps.ready && !ps.ready(g)) return fail(VR_ERR_STATE, "no %s set (%s)", ps.state, ps.setters);
     if (b.buf && (b.nx != v.nx || b.ny != v.ny || b.nz != v.nz))
         return fail(VR_ERR_STATE, "the GMM planes hold a %d x %d x %d volume, the resident records "
-                    "are of %d x %d x %d: %s first", b.nx, b.ny, b.nz, v.nx, v.ny, v.nz,
-                    quant ? "vr_release_gmm_quantile"
-                          : range ? "vr_release_gmm_range" : "vr_release_gmm_stats");
+                    "are of %d x %d x %d: %s first", b.nx, b.ny, b.nz, v.nx, v.ny, v.nz, ps.release);
     if (v.nx > 65535 || v.ny > 65535 || v.nzs > 65535)
         return fail(VR_ERR_UNSUPPORTED, "baking GMM volumes beyond 65535 voxels per axis");
     uint64_t psy = b.sy, psz = b.sz, plane = b.plane;
@@ -2431,28 +2477,21 @@ int bake_gmm_planes(State::GmmStats &b, GmmBake kind) {
     if (!buf) {
         vr::plane_pitches((uint32_t)v.nx, (uint32_t)v.ny, psy, psz);
         plane = psz * (uint64_t)v.nz;
-        VR_HIP(hipMalloc(&buf, (nplanes * plane + 4) * sizeof(float)));
+        VR_HIP(hipMalloc(&buf, (ps.nplanes * plane + 4) * sizeof(float)));
         // (the planes' padding is read with weight 0: it must hold finite floats)
-        const hipError_t e = hipMemsetAsync(buf, 0, (nplanes * plane + 4) * sizeof(float), g.stream);
+        const hipError_t e = hipMemsetAsync(buf, 0, (ps.nplanes * plane + 4) * sizeof(float), g.stream);
         if (e != hipSuccess) {
             (void)hipFree(buf);
-            return hip_fail(e, fn);
+            return hip_fail(e, ps.bake);
         }
     }
-    const hipError_t e =
-        quant ? vr::launch_bake_gmm_quant(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
-                                          g.qq, g.qmode == 2, buf, psy, psz, g.stream)
-        : range ? vr::launch_bake_gmm_range(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs,
-                                            g.grq, buf, psy, psz, g.stream)
-                : vr::launch_bake_gmm(v.wm, v.sg, gmm_f16(), v.K, v.nx, v.ny, v.z_base, v.nzs, buf,
-                                      plane, psy, psz, g.stream);
+    const hipError_t e = ps.bake_launch(buf, plane, psy, psz);
     if (e != hipSuccess) {
         if (!b.buf) {  // the planes this call allocated, once their memset has run
             (void)hipStreamSynchronize(g.stream);
             (void)hipFree(buf);
         }
-        return hip_fail(e, quant ? "launch(k_bake_gmm_quant)"
-                           : range ? "launch(k_bake_gmm_range)" : "launch(k_bake_gmm)");
+        return hip_fail(e, ps.bake_kernel);
     }
     if (!b.buf) {
         b.buf = buf;
@@ -2471,8 +2510,10 @@ int bake_gmm_planes(State::GmmStats &b, GmmBake kind) {
     return VR_OK;
 }
 
-void gmm_planes_info(const State::GmmStats &b, vr_extent *dims, const float **d_planes,
-                     uint64_t *plane_floats, int *slices_baked) {
+// vr_gmm_*_info of a set
+int gmm_planes_info(int set, vr_extent *dims, const float **d_planes, uint64_t *plane_floats,
+                    int *slices_baked) {
+    const State::GmmStats &b = g.gplanes[set];
     if (dims) {
         dims->width = (size_t)b.nx;
         dims->height = (size_t)b.ny;
@@ -2481,13 +2522,14 @@ void gmm_planes_info(const State::GmmStats &b, vr_extent *dims, const float **d_
     if (d_planes) *d_planes = b.buf;
     if (plane_floats) *plane_floats = b.plane;
     if (slices_baked) *slices_baked = b.nbaked;
+    return VR_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
-int vr_bake_gmm_stats(void) { return bake_gmm_planes(g.gstats, kBakeStats); }
+int vr_bake_gmm_stats(void) { return bake_gmm_planes(State::kGmmStats); }
 
 // ---- range probability of GMM volumes ----
 // host state only: no HIP call (the plane a set or clear drops is freed, if any)
@@ -2495,14 +2537,14 @@ int vr_set_gmm_range(float lo, float hi) {
     if (lo != lo || hi != hi || lo > hi)
         return fail(VR_ERR_ARG, "vr_set_gmm_range: bounds [%g, %g) (NaN or lo > hi)", (double)lo,
                     (double)hi);
-    release_gmm_range();
+    release_gmm_set(State::kGmmRange);
     g.grq = vr::GmmRange{lo, hi};
     g.grq_set = true;
     return VR_OK;
 }
 
 int vr_clear_gmm_range(void) {
-    release_gmm_range();
+    release_gmm_set(State::kGmmRange);
     g.grq = vr::GmmRange{};
     g.grq_set = false;
     return VR_OK;
@@ -2523,45 +2565,33 @@ int vr_gmm_phi_table(const float **c, int *nseg, float *h, float *zmax) {
     return VR_OK;
 }
 
-int vr_bake_gmm_range(void) { return bake_gmm_planes(g.grange, kBakeRange); }
+int vr_bake_gmm_range(void) { return bake_gmm_planes(State::kGmmRange); }
 
-int vr_release_gmm_range(void) {
-    release_gmm_range();
-    return VR_OK;
-}
+int vr_release_gmm_range(void) { return release_gmm_set(State::kGmmRange); }
 
 int vr_gmm_range_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
                       int *slices_baked) {
-    gmm_planes_info(g.grange, dims, d_plane, plane_floats, slices_baked);
-    return VR_OK;
+    return gmm_planes_info(State::kGmmRange, dims, d_plane, plane_floats, slices_baked);
 }
 
 // ---- quantile of GMM volumes: the quantile itself is the
 // state of vr_set_quantile / vr_set_quantile_spread / vr_clear_quantile ----
 int vr_gmm_quantile_steps(void) { return vr::kGmmQuantSteps; }
 
-int vr_bake_gmm_quantile(void) { return bake_gmm_planes(g.gquant, kBakeQuantile); }
+int vr_bake_gmm_quantile(void) { return bake_gmm_planes(State::kGmmQuant); }
 
-int vr_release_gmm_quantile(void) {
-    release_gmm_quantile();
-    return VR_OK;
-}
+int vr_release_gmm_quantile(void) { return release_gmm_set(State::kGmmQuant); }
 
 int vr_gmm_quantile_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
                          int *slices_baked) {
-    gmm_planes_info(g.gquant, dims, d_plane, plane_floats, slices_baked);
-    return VR_OK;
+    return gmm_planes_info(State::kGmmQuant, dims, d_plane, plane_floats, slices_baked);
 }
 
-int vr_release_gmm_stats(void) {
-    release_gmm_stats();
-    return VR_OK;
-}
+int vr_release_gmm_stats(void) { return release_gmm_set(State::kGmmStats); }
 
 int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_floats,
                       int *slices_baked) {
-    gmm_planes_info(g.gstats, dims, d_planes, plane_floats, slices_baked);
-    return VR_OK;
+    return gmm_planes_info(State::kGmmStats, dims, d_planes, plane_floats, slices_baked);
 }
 
 // A frame of method 1 / 2 from the baked GMM planes: vr_render's plane march
@@ -2571,67 +2601,38 @@ int vr_gmm_stats_info(vr_extent *dims, const float **d_planes, uint64_t *plane_f
 // F = P(v < theta) it is after vr_set_gmm_range(-inf, theta).
 int vr_render_gmm_baked(const vr_render_desc *desc) {
     if (!desc) return fail(VR_ERR_ARG, "null render descriptor");
-    const bool cross = desc->query_method == VR_QUERY_CROSSING;
-    const bool range = cross || desc->query_method == VR_QUERY_WEIGHTED;
-    const bool quant = desc->query_method == VR_QUERY_QUANTILE;
-    // (the plane march is planned as method 1 for the range and quantile planes:
-    // each is one float per voxel like the mean's)
-    const int qm = range || quant ? 1 : desc->query_method;
-    if (qm != 1 && qm != 2)
+    const int set = gmm_plane_set(desc->query_method);
+    if (set < 0)
         return fail(VR_ERR_UNSUPPORTED, "baked GMM frames support queryMethod 1 (mean), 2 "
                     "(variance), 10 (range probability), 11 (quantile) and 13 (level "
                     "crossing)");
-    const State::GmmStats &b = quant ? g.gquant : range ? g.grange : g.gstats;
-    if (!b.buf)
-        return fail(VR_ERR_STATE, quant ? "no baked GMM quantile plane (vr_bake_gmm_quantile first)"
-                                  : range ? "no baked GMM range plane (vr_bake_gmm_range first)"
-                                          : "no baked GMM planes (vr_bake_gmm_stats first)");
+    // the plane of the set: method - 1 of the mean / variance pair, the only one of
+    // the others (the plane march is planned as method 1 for those: each is one
+    // float per voxel like the mean's)
+    const int plane = set == State::kGmmStats ? desc->query_method - 1 : 0;
+    const GmmPlaneSet &ps = kGmmPlaneSets[set];
+    const State::GmmStats &b = g.gplanes[set];
+    if (!b.buf) return fail(VR_ERR_STATE, "no baked GMM %s (%s first)", ps.planes, ps.bake);
     if (b.nbaked != b.nz)
         return fail(VR_ERR_STATE, "%d of the GMM planes' %d slices are baked", b.nbaked, b.nz);
     vr::Params P;
     uint32_t nslots = 0;
     const FrameVol v = {b.nx, b.ny, b.nz, 1, b.sy, b.sz};
     vr_render_desc as_plane = *desc;  // (methods 10 / 11 here are not the record volumes' queries)
-    as_plane.query_method = qm;
+    as_plane.query_method = plane + 1;
     int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
-    if (cross) {  // no plan: the one-lane march on the x-row bricks for every view
-        const hipError_t e = vr::launch_march_cross_plane(b.buf, P, nslots, g.stream);
+    const float *pl = b.buf + (uint64_t)plane * b.plane;
+    hipError_t e;
+    if (desc->query_method == VR_QUERY_CROSSING) {
+        // no plan: the one-lane march on the x-row bricks for every view
+        e = vr::launch_march_cross_plane(pl, P, nslots, g.stream);
         if (e != hipSuccess) return hip_fail(e, "launch(k_march_cross_plane)");
-        if (P.tile_cost) g.cost_recorded = true;
-        return VR_OK;
+    } else {
+        rc = launch_plane_frame(desc, P, nslots, pl, b.sy, b.sz, e);
+        if (rc != VR_OK) return rc;
+        if (e != hipSuccess) return hip_fail(e, "launch(k_march)");
     }
-    vr::PlanIn in = {};
-    in.m0 = desc->inv_view[0];
-    in.m4 = desc->inv_view[4];
-    in.m8 = desc->inv_view[8];
-    in.W = desc->width;
-    in.H = desc->height;
-    in.CW = P.CW;
-    in.CH = P.CH;
-    in.tile_list = desc->d_tile_list != nullptr;
-    in.n_tiles = desc->n_tiles;
-    in.method = qm;
-    in.nb = 1;
-    in.nx = b.nx;
-    in.ny = b.ny;
-    in.nz = b.nz;
-    in.owned = false;
-    in.f16 = false;
-    in.baked = true;
-    in.plane_sy = b.sy;
-    in.plane_sz = b.sz;
-    in.count = false;
-    // the x-row bricks only: no layout copies of GMM planes
-    in.denied = vr::kLayoutAxis | vr::kLayoutBrick | vr::kLayoutPlane;
-    in.tuning = vr::tuning;
-    const vr::MarchPlan pl = vr::plan_march(in);
-    if (pl.layout != vr::kLayoutNone || pl.method > 0)
-        return fail(VR_ERR_UNSUPPORTED, "no plane march for this frame of the GMM planes");
-    apply_plan(pl, P);
-    const hipError_t e = vr::launch_plan(pl, b.buf + (uint64_t)(qm - 1) * b.plane, P, nslots,
-                                         g.stream);
-    if (e != hipSuccess) return hip_fail(e, "launch(k_march)");
     if (P.tile_cost) g.cost_recorded = true;
     return VR_OK;
 }
@@ -2748,9 +2749,7 @@ void freeCudaBuffers(void) {
     release_codec();
     release_flex();
     release_all_gmm();
-    release_gmm_stats();
-    release_gmm_range();
-    release_gmm_quantile();
+    for (int set = 0; set < State::kGmmSets; set++) release_gmm_set(set);
 }
 
 void setTextureFilterMode(bool bLinearFilter) { g.linear_filter = bLinearFilter; }
@@ -2853,7 +2852,7 @@ bool quantile_ok(float q) { return std::isfinite(q) && q >= 0.0f && q <= 1.0f; }
 int vr_set_quantile(float q) {
     if (!quantile_ok(q)) return fail(VR_ERR_ARG, "vr_set_quantile: q must be in [0, 1]");
     release_planes(query_plane(VR_QUERY_QUANTILE));  // a plane baked for another quantile
-    release_gmm_quantile();
+    release_gmm_set(State::kGmmQuant);
     g.qq = vr::QuantArgs{q, q};
     g.qmode = 1;
     return VR_OK;
@@ -2863,7 +2862,7 @@ int vr_set_quantile_spread(float q_lo, float q_hi) {
     if (!quantile_ok(q_lo) || !quantile_ok(q_hi) || q_lo > q_hi)
         return fail(VR_ERR_ARG, "vr_set_quantile_spread: 0 <= q_lo <= q_hi <= 1 required");
     release_planes(query_plane(VR_QUERY_QUANTILE));
-    release_gmm_quantile();
+    release_gmm_set(State::kGmmQuant);
     g.qq = vr::QuantArgs{q_lo, q_hi};
     g.qmode = 2;
     return VR_OK;
@@ -2871,7 +2870,7 @@ int vr_set_quantile_spread(float q_lo, float q_hi) {
 
 int vr_clear_quantile(void) {
     release_planes(query_plane(VR_QUERY_QUANTILE));
-    release_gmm_quantile();
+    release_gmm_set(State::kGmmQuant);
     g.qq = vr::QuantArgs{};
     g.qmode = 0;
     return VR_OK;

@@ -61,6 +61,12 @@
 // Quantile (query method 11): GmmQuantStat is the value at
 // which the mixture's CDF, built of the same table, reaches q W -- a bisection of
 // kGmmQuantSteps steps over the support [a0, b0] -- or the difference of two.
+//
+// What the statistics share: gmm_march is every march and
+// gmm_bake_voxel every bake kernel's body -- a __global__ stages the table if its
+// statistic reads it and names the functor; with_gmm_k / with_gmm_records /
+// with_gmm_march turn K, the element type and SPREAD into a compiled instance
+// for all six launchers, and bake_gmm_grid is the grid of the three bakes.
 #include "vr_half.h"
 #include "vr_internal.h"
 #include "vr_march.h"
@@ -580,115 +586,114 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VR_GMMH_WAV
     gmm_march<_Float16, K, GmmQuantStat<SPREAD>, false>(P, GmmQuantStat<SPREAD>{Q.q_lo, Q.q_hi, tab});
 }
 
-template <bool HALF, int K, int M, bool COUNT>
-static void launch_gmm_km(const Params &P, uint32_t nblocks, hipStream_t s) {
-    if constexpr (HALF)
-        hipLaunchKernelGGL((k_march_gmm_h<K, M, COUNT>), dim3(nblocks), dim3(256), occupancy_lds(P), s, P);
-    else
-        hipLaunchKernelGGL((k_march_gmm<K, M, COUNT>), dim3(nblocks), dim3(256), occupancy_lds(P), s, P);
+// ---- launchers: one dispatch for every statistic ----
+// The component counts the kernels are compiled for: f(std::integral_constant<int,
+// K>{}) and what it returns (launched); false, nothing called: no instance for K.
+// (The order of the lists here and below, and of the launchers in this file, is
+// the order of instantiation and so of the kernels in the code object, last named
+// first; the kernels that read the table address it relative to where they lie.)
+template <typename F>
+inline bool with_gmm_k(int K, F &&f) {
+    return with_value<32, 16, 8>(K, f);
 }
 
-template <bool HALF, int K>
-static hipError_t launch_gmm_k(int method, const Params &P, uint32_t nblocks, bool count,
-                               hipStream_t s) {
-    const char *name = HALF ? "k_march_gmm_h" : "k_march_gmm";
-    if (count) {  // the samples (and so the footprints) depend on the statistic
-        if (method == 1) launch_gmm_km<HALF, K, 1, true>(P, nblocks, s);
-        else if (method == 2) launch_gmm_km<HALF, K, 2, true>(P, nblocks, s);
-        else return hipErrorInvalidValue;
-    } else if (method == 1) {
-        note_kernel(name, K, 1);
-        launch_gmm_km<HALF, K, 1, false>(P, nblocks, s);
-    } else if (method == 2) {
-        note_kernel(name, K, 2);
-        launch_gmm_km<HALF, K, 2, false>(P, nblocks, s);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+// ... and the planes' element type with them: f(wm, sg, k), the planes as
+// const _Float16 * or const float * (ElemOf<decltype(wm)>: that type)
+template <typename F>
+inline bool with_gmm_records(const void *wm, const void *sg, bool half, int K, F &&f) {
+    if (half)
+        return with_gmm_k(K, [&](auto k) {
+            f(static_cast<const _Float16 *>(wm), static_cast<const _Float16 *>(sg), k);
+            return true;
+        });
+    return with_gmm_k(K, [&](auto k) {
+        f(static_cast<const float *>(wm), static_cast<const float *>(sg), k);
+        return true;
+    });
 }
 
-template <bool HALF>
-static hipError_t launch_gmm_t(int K, int method, const Params &P, uint32_t nblocks, bool count,
-                               hipStream_t s) {
-    switch (K) {
-    case 8: return launch_gmm_k<HALF, 8>(method, P, nblocks, count, s);
-    case 16: return launch_gmm_k<HALF, 16>(method, P, nblocks, count, s);
-    case 32: return launch_gmm_k<HALF, 32>(method, P, nblocks, count, s);
-    default: return hipErrorInvalidValue;
-    }
+// ... and for a march, whose f16 kernel is a __global__ of its own (its register
+// budget differs): f(h, k), h 1 for f16 planes
+template <typename F>
+inline bool with_gmm_march(bool half, int K, F &&f) {
+    return with_value<0, 1>(half, [&](auto h) {
+        return with_gmm_k(K, [&](auto k) { return f(h, k); });
+    });
+}
+
+// the LDS request of a march that stages the table: the VR_WG_PER_CU request leaves
+// room for the kernel's static copy
+static size_t phi_march_lds(const Params &P) {
+    return cap_lds(P, P.wg_per_cu, 0, sizeof(float) * 4 * kPhiRows);
 }
 
 hipError_t launch_march_gmm(int K, int method, bool half, const Params &P, uint32_t nblocks,
                             bool count, hipStream_t s) {
     if (nblocks == 0) return hipSuccess;
-    return half ? launch_gmm_t<true>(K, method, P, nblocks, count, s)
-                : launch_gmm_t<false>(K, method, P, nblocks, count, s);
-}
-
-template <bool HALF, int K>
-static void launch_gmm_range_k(const Params &P, const GmmRange &Q, uint32_t nblocks, hipStream_t s) {
-    // the VR_WG_PER_CU request leaves room for the kernel's static table
-    const size_t lds = cap_lds(P, P.wg_per_cu, 0, sizeof(float) * 4 * kPhiRows);
-    if constexpr (HALF)
-        hipLaunchKernelGGL((k_march_gmm_range_h<K>), dim3(nblocks), dim3(256), lds, s, P, Q);
-    else
-        hipLaunchKernelGGL((k_march_gmm_range<K>), dim3(nblocks), dim3(256), lds, s, P, Q);
-}
-
-template <bool HALF>
-static hipError_t launch_gmm_range_t(int K, const Params &P, const GmmRange &Q, uint32_t nblocks,
-                                     hipStream_t s) {
-    switch (K) {
-    case 8: launch_gmm_range_k<HALF, 8>(P, Q, nblocks, s); break;
-    case 16: launch_gmm_range_k<HALF, 16>(P, Q, nblocks, s); break;
-    case 32: launch_gmm_range_k<HALF, 32>(P, Q, nblocks, s); break;
-    default: return hipErrorInvalidValue;
-    }
-    note_kernel(HALF ? "k_march_gmm_range_h" : "k_march_gmm_range", K, 10);
+    const dim3 grid(nblocks), block(256);
+    const size_t lds = occupancy_lds(P);
+    // (a count has instances of its own: the samples, and so the footprints, depend
+    // on the statistic)
+    if (!with_gmm_march(half, K, [&](auto h, auto k) {
+            return with_value<0, 1>(count, [&](auto c) {
+                return with_value<2, 1>(method, [&](auto m) {
+                    constexpr int KK = decltype(k)::value, M = decltype(m)::value;
+                    constexpr bool H = decltype(h)::value != 0, C = decltype(c)::value != 0;
+                    if constexpr (!C) note_kernel(H ? "k_march_gmm_h" : "k_march_gmm", KK, M);
+                    if constexpr (H)
+                        hipLaunchKernelGGL((k_march_gmm_h<KK, M, C>), grid, block, lds, s, P);
+                    else
+                        hipLaunchKernelGGL((k_march_gmm<KK, M, C>), grid, block, lds, s, P);
+                    return true;
+                });
+            });
+        }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
 hipError_t launch_march_gmm_range(int K, bool half, const Params &P, const GmmRange &Q,
                                   uint32_t nblocks, hipStream_t s) {
     if (nblocks == 0) return hipSuccess;
-    return half ? launch_gmm_range_t<true>(K, P, Q, nblocks, s)
-                : launch_gmm_range_t<false>(K, P, Q, nblocks, s);
-}
-
-template <bool HALF, int K, bool SPREAD>
-static void launch_gmm_quant_k(const Params &P, const QuantArgs &Q, uint32_t nblocks, hipStream_t s) {
-    const size_t lds = cap_lds(P, P.wg_per_cu, 0, sizeof(float) * 4 * kPhiRows);
-    if constexpr (HALF)
-        hipLaunchKernelGGL((k_march_gmm_quant_h<K, SPREAD>), dim3(nblocks), dim3(256), lds, s, P, Q);
-    else
-        hipLaunchKernelGGL((k_march_gmm_quant<K, SPREAD>), dim3(nblocks), dim3(256), lds, s, P, Q);
-}
-
-template <bool HALF, bool SPREAD>
-static hipError_t launch_gmm_quant_t(int K, const Params &P, const QuantArgs &Q, uint32_t nblocks,
-                                     hipStream_t s) {
-    switch (K) {
-    case 8: launch_gmm_quant_k<HALF, 8, SPREAD>(P, Q, nblocks, s); break;
-    case 16: launch_gmm_quant_k<HALF, 16, SPREAD>(P, Q, nblocks, s); break;
-    case 32: launch_gmm_quant_k<HALF, 32, SPREAD>(P, Q, nblocks, s); break;
-    default: return hipErrorInvalidValue;
-    }
-    note_kernel(HALF ? "k_march_gmm_quant_h" : "k_march_gmm_quant", K, 11);
+    const dim3 grid(nblocks), block(256);
+    const size_t lds = phi_march_lds(P);
+    if (!with_gmm_march(half, K, [&](auto h, auto k) {
+            constexpr int KK = decltype(k)::value;
+            if constexpr (decltype(h)::value != 0)
+                hipLaunchKernelGGL((k_march_gmm_range_h<KK>), grid, block, lds, s, P, Q);
+            else
+                hipLaunchKernelGGL((k_march_gmm_range<KK>), grid, block, lds, s, P, Q);
+            return true;
+        }))
+        return hipErrorInvalidValue;
+    note_kernel(half ? "k_march_gmm_range_h" : "k_march_gmm_range", K, 10);
     return hipGetLastError();
 }
 
 hipError_t launch_march_gmm_quant(int K, bool half, const Params &P, const QuantArgs &Q,
                                   bool spread, uint32_t nblocks, hipStream_t s) {
     if (nblocks == 0) return hipSuccess;
-    if (half)
-        return spread ? launch_gmm_quant_t<true, true>(K, P, Q, nblocks, s)
-                      : launch_gmm_quant_t<true, false>(K, P, Q, nblocks, s);
-    return spread ? launch_gmm_quant_t<false, true>(K, P, Q, nblocks, s)
-                  : launch_gmm_quant_t<false, false>(K, P, Q, nblocks, s);
+    const dim3 grid(nblocks), block(256);
+    const size_t lds = phi_march_lds(P);
+    if (!with_value<0, 1>(half, [&](auto h) {
+            return with_value<0, 1>(spread, [&](auto sp) {
+                return with_gmm_k(K, [&](auto k) {
+                    constexpr int KK = decltype(k)::value;
+                    constexpr bool SP = decltype(sp)::value != 0;
+                    if constexpr (decltype(h)::value != 0)
+                        hipLaunchKernelGGL((k_march_gmm_quant_h<KK, SP>), grid, block, lds, s, P, Q);
+                    else
+                        hipLaunchKernelGGL((k_march_gmm_quant<KK, SP>), grid, block, lds, s, P, Q);
+                    return true;
+                });
+            });
+        }))
+        return hipErrorInvalidValue;
+    note_kernel(half ? "k_march_gmm_quant_h" : "k_march_gmm_quant", K, 11);
+    return hipGetLastError();
 }
 
-// ---- baked GMM statistics (vr_bake_gmm_stats) ----
+// ---- baked GMM statistics (vr_bake_gmm_*, DESIGN.md sections 15, 18.3, 19.3) ----
 // The mean and the 16 x variance the march decodes at every corner are pure
 // functions of one voxel's record, so one pass over the resident records
 // decodes them once into two float planes in the 16 x 2 x 1 bricks of the
@@ -696,221 +701,163 @@ hipError_t launch_march_gmm_quant(int K, bool half, const Params &P, const Quant
 // frame is then the plane march of vr_kernels.hip / vr_seg.hip on plane
 // method - 1.  The planes hold the bits gmm_stat<L, 1> and gmm_stat<L, 2>
 // return: the same L = K/4 lanes per voxel, the same partials and DPP sums.
+// The range probability and the quantile go into one plane each the same way.
 //
 // A wave takes 64/L consecutive x voxels of one row, a workgroup 4 waves of
 // the same row (grid: x chunks, y rows, resident slices).  Lane s of a group
 // loads components 4s .. 4s + 3, so the wave's loads are contiguous: one row
 // segment of (w, mu) (fp32: 2 x 16 B per lane, f16: 16 B) and one of sigma (16 /
-// 8 B), each record read once for both planes.  The whole group must reach the
+// 8 B), each record read once for every plane.  The whole group must reach the
 // DPP sums: a lane past the row's end decodes the row's last voxel (clamped
 // address) and skips the store; only a wave wholly past the end leaves.
 // Records are indexed by z - z_base (gmm_vox), the planes by the volume's z.
+
+// The body of a bake kernel: the mapping above and the load of the lane's chunk of
+// its voxel's record, both planes; then f(r, put), for every lane of the groups of a
+// wave that has voxels (a wave wholly past the row's end has left: wave-uniform).
+// put(out, v) stores the voxel's statistic v into the plane at out, by the first
+// lane of a group whose voxel lies in the row.
+template <typename T, int K, typename F>
+__device__ __forceinline__ void gmm_bake_voxel(const T *__restrict__ wm, const T *__restrict__ sg,
+                                               uint32_t nx, uint32_t ny, uint32_t z_base,
+                                               uint64_t psy, uint64_t psz, F &&f) {
+    constexpr int L = K / 4;              // lanes per voxel
+    constexpr uint32_t R = 64u / L;       // voxels per wave
+    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sub = lane % L;
+    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
+    if (x0 >= nx) return;                 // wave-uniform
+    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
+    const bool in = x < nx;
+    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
+    GmmPart<T, 2> r;
+    if constexpr (sizeof(T) == 4) {
+        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
+        r.wm[0] = a[0];
+        r.wm[1] = a[1];
+        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
+    } else {
+        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
+        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
+    }
+    f(r, [&](float *out, float stat) {
+        if (in && sub == 0) put_plane(out, x, y, z_base + zl, psy, psz, stat);
+    });
+}
+
+// the bake of one plane of statistic st (every lane of a group calls stat<L>)
+template <typename T, int K, typename S>
+__device__ __forceinline__ void gmm_bake_stat(const T *__restrict__ wm, const T *__restrict__ sg,
+                                              uint32_t nx, uint32_t ny, uint32_t z_base,
+                                              const S &st, float *__restrict__ out, uint64_t psy,
+                                              uint64_t psz) {
+    gmm_bake_voxel<T, K>(wm, sg, nx, ny, z_base, psy, psz, [&](const GmmPart<T, 2> &r, auto put) {
+        put(out, st.template stat<K / 4>(r));
+    });
+}
+
 template <typename T, int K>
 __global__ __launch_bounds__(256) void k_bake_gmm(const T *__restrict__ wm,
                                                   const T *__restrict__ sg, uint32_t nx,
                                                   uint32_t ny, uint32_t z_base,
                                                   float *__restrict__ out, uint64_t plane,
                                                   uint64_t psy, uint64_t psz) {
-    constexpr int L = K / 4;              // lanes per voxel
-    constexpr uint32_t R = 64u / L;       // voxels per wave
-    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane % L;
-    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
-    if (x0 >= nx) return;                 // wave-uniform
-    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
-    const bool in = x < nx;
-    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
-    GmmPart<T, 2> r;
-    GmmPart<T, 1> rm;                     // the same (w, mu): the mean's operand type
-    if constexpr (sizeof(T) == 4) {
-        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
-        r.wm[0] = a[0];
-        r.wm[1] = a[1];
-        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
-        rm.wm[0] = r.wm[0];
-        rm.wm[1] = r.wm[1];
-    } else {
-        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
-        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
-        rm.wm = r.wm;
-    }
-    const float m = gmm_stat<L, 1>(rm);
-    const float v16 = gmm_stat<L, 2>(r);
-    if (in && sub == 0) {
-        const uint32_t z = z_base + zl;
-        put_plane(out, x, y, z, psy, psz, m);
-        put_plane(out + plane, x, y, z, psy, psz, v16);
-    }
+    gmm_bake_voxel<T, K>(wm, sg, nx, ny, z_base, psy, psz, [&](const GmmPart<T, 2> &r, auto put) {
+        GmmPart<T, 1> rm;                 // the same (w, mu): the mean's operand type
+        if constexpr (sizeof(T) == 4) {
+            rm.wm[0] = r.wm[0];
+            rm.wm[1] = r.wm[1];
+        } else {
+            rm.wm = r.wm;
+        }
+        const float m = gmm_stat<K / 4, 1>(rm);
+        const float v16 = gmm_stat<K / 4, 2>(r);
+        put(out, m);
+        put(out + plane, v16);
+    });
 }
 
-// The range probability of every resident voxel into one plane: k_bake_gmm's
-// mapping and loads, GmmRangeStat's arithmetic.  The table is staged before a
-// wave past the row's end leaves.
+// The range probability of every resident voxel into one plane.  The table is
+// staged before a wave past the row's end leaves (phi_stage's barrier).
 template <typename T, int K>
 __global__ __launch_bounds__(256) void k_bake_gmm_range(const T *__restrict__ wm,
                                                         const T *__restrict__ sg, uint32_t nx,
                                                         uint32_t ny, uint32_t z_base, GmmRange Q,
                                                         float *__restrict__ out, uint64_t psy,
                                                         uint64_t psz) {
-    constexpr int L = K / 4;              // lanes per voxel
-    constexpr uint32_t R = 64u / L;       // voxels per wave
-    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
     __shared__ float tab[4 * kPhiRows];
     phi_stage(tab);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane % L;
-    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
-    if (x0 >= nx) return;                 // wave-uniform
-    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
-    const bool in = x < nx;
-    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
-    GmmPart<T, 2> r;
-    if constexpr (sizeof(T) == 4) {
-        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
-        r.wm[0] = a[0];
-        r.wm[1] = a[1];
-        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
-    } else {
-        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
-        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
-    }
-    const float p = GmmRangeStat{Q.lo, Q.hi, tab}.template stat<L>(r);
-    if (in && sub == 0) put_plane(out, x, y, z_base + zl, psy, psz, p);
+    gmm_bake_stat<T, K>(wm, sg, nx, ny, z_base, GmmRangeStat{Q.lo, Q.hi, tab}, out, psy, psz);
 }
 
-template <typename T>
-static hipError_t launch_bake_gmm_range_t(const T *wm, const T *sg, int K, uint32_t nx, uint32_t ny,
-                                          uint32_t z_base, uint32_t nzs, const GmmRange &Q,
-                                          float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
-    const uint32_t per_wg = 4u * 64u / (uint32_t)(K / 4);  // voxels of a row per workgroup
-    const dim3 grid((nx + per_wg - 1) / per_wg, ny, nzs), block(256);
-    switch (K) {
-    case 8: hipLaunchKernelGGL((k_bake_gmm_range<T, 8>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
-    case 16: hipLaunchKernelGGL((k_bake_gmm_range<T, 16>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
-    case 32: hipLaunchKernelGGL((k_bake_gmm_range<T, 32>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_bake_gmm_range(const void *wm, const void *sg, bool half, int K, int nx, int ny,
-                                 int z_base, int nzs, const GmmRange &Q, float *out, uint64_t psy,
-                                 uint64_t psz, hipStream_t s) {
-    if (nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 || nzs > 65535)
-        return hipErrorInvalidValue;
-    if (half)
-        return launch_bake_gmm_range_t(static_cast<const _Float16 *>(wm),
-                                       static_cast<const _Float16 *>(sg), K, (uint32_t)nx,
-                                       (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, Q, out, psy,
-                                       psz, s);
-    return launch_bake_gmm_range_t(static_cast<const float *>(wm), static_cast<const float *>(sg), K,
-                                   (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, Q,
-                                   out, psy, psz, s);
-}
-
-// The quantile of every resident voxel into one plane: k_bake_gmm_range's mapping,
-// loads and store, GmmQuantStat's arithmetic.
+// ... and the quantile, the table staged as above
 template <typename T, int K, bool SPREAD>
 __global__ __launch_bounds__(256) void k_bake_gmm_quant(const T *__restrict__ wm,
                                                         const T *__restrict__ sg, uint32_t nx,
                                                         uint32_t ny, uint32_t z_base, QuantArgs Q,
                                                         float *__restrict__ out, uint64_t psy,
                                                         uint64_t psz) {
-    constexpr int L = K / 4;              // lanes per voxel
-    constexpr uint32_t R = 64u / L;       // voxels per wave
-    static_assert(L == 2 || L == 4 || L == 8, "K = 8, 16 or 32");
     __shared__ float tab[4 * kPhiRows];
     phi_stage(tab);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane % L;
-    const uint32_t x0 = (blockIdx.x * 4u + wave) * R;
-    if (x0 >= nx) return;                 // wave-uniform
-    const uint32_t x = x0 + lane / L, y = blockIdx.y, zl = blockIdx.z;
-    const bool in = x < nx;
-    const uint64_t v = ((uint64_t)zl * ny + y) * nx + (in ? x : nx - 1u);
-    GmmPart<T, 2> r;
-    if constexpr (sizeof(T) == 4) {
-        const float4 *a = reinterpret_cast<const float4 *>(wm + v * (2u * K)) + sub * 2u;
-        r.wm[0] = a[0];
-        r.wm[1] = a[1];
-        r.sg[0] = reinterpret_cast<const float4 *>(sg + v * K)[sub];
-    } else {
-        r.wm = reinterpret_cast<const uint4 *>(wm + v * (2u * K))[sub];
-        r.sg = reinterpret_cast<const uint2 *>(sg + v * K)[sub];
-    }
-    const float q = GmmQuantStat<SPREAD>{Q.q_lo, Q.q_hi, tab}.template stat<L>(r);
-    if (in && sub == 0) put_plane(out, x, y, z_base + zl, psy, psz, q);
+    gmm_bake_stat<T, K>(wm, sg, nx, ny, z_base, GmmQuantStat<SPREAD>{Q.q_lo, Q.q_hi, tab}, out,
+                        psy, psz);
 }
 
-template <typename T, bool SPREAD>
-static hipError_t launch_bake_gmm_quant_t(const T *wm, const T *sg, int K, uint32_t nx, uint32_t ny,
-                                          uint32_t z_base, uint32_t nzs, const QuantArgs &Q,
-                                          float *out, uint64_t psy, uint64_t psz, hipStream_t s) {
+// the grid of a bake launch; false: no such K, or more voxels along an axis than a
+// grid (y / z: rows and slices) or a plane brick index (plane_bx: x < 2^16) takes
+static bool bake_gmm_grid(int K, int nx, int ny, int z_base, int nzs, dim3 &grid) {
+    if (K < 4 || nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 ||
+        nzs > 65535)
+        return false;
     const uint32_t per_wg = 4u * 64u / (uint32_t)(K / 4);  // voxels of a row per workgroup
-    const dim3 grid((nx + per_wg - 1) / per_wg, ny, nzs), block(256);
-    switch (K) {
-    case 8: hipLaunchKernelGGL((k_bake_gmm_quant<T, 8, SPREAD>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
-    case 16: hipLaunchKernelGGL((k_bake_gmm_quant<T, 16, SPREAD>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
-    case 32: hipLaunchKernelGGL((k_bake_gmm_quant<T, 32, SPREAD>), grid, block, 0, s, wm, sg, nx, ny, z_base, Q, out, psy, psz); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    grid = dim3(((uint32_t)nx + per_wg - 1) / per_wg, (uint32_t)ny, (uint32_t)nzs);
+    return true;
 }
 
-template <bool SPREAD>
-static hipError_t launch_bake_gmm_quant_s(const void *wm, const void *sg, bool half, int K,
-                                          uint32_t nx, uint32_t ny, uint32_t z_base, uint32_t nzs,
-                                          const QuantArgs &Q, float *out, uint64_t psy, uint64_t psz,
-                                          hipStream_t s) {
-    if (half)
-        return launch_bake_gmm_quant_t<_Float16, SPREAD>(static_cast<const _Float16 *>(wm),
-                                                         static_cast<const _Float16 *>(sg), K, nx, ny,
-                                                         z_base, nzs, Q, out, psy, psz, s);
-    return launch_bake_gmm_quant_t<float, SPREAD>(static_cast<const float *>(wm),
-                                                  static_cast<const float *>(sg), K, nx, ny, z_base,
-                                                  nzs, Q, out, psy, psz, s);
+hipError_t launch_bake_gmm_range(const void *wm, const void *sg, bool half, int K, int nx, int ny,
+                                 int z_base, int nzs, const GmmRange &Q, float *out, uint64_t psy,
+                                 uint64_t psz, hipStream_t s) {
+    dim3 grid;
+    if (!bake_gmm_grid(K, nx, ny, z_base, nzs, grid) ||
+        !with_gmm_records(wm, sg, half, K, [&](auto w, auto g, auto k) {
+            hipLaunchKernelGGL((k_bake_gmm_range<ElemOf<decltype(w)>, decltype(k)::value>), grid,
+                               dim3(256), 0, s, w, g, (uint32_t)nx, (uint32_t)ny,
+                               (uint32_t)z_base, Q, out, psy, psz);
+        }))
+        return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
 hipError_t launch_bake_gmm_quant(const void *wm, const void *sg, bool half, int K, int nx, int ny,
                                  int z_base, int nzs, const QuantArgs &Q, bool spread, float *out,
                                  uint64_t psy, uint64_t psz, hipStream_t s) {
-    if (nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 || nzs > 65535)
+    dim3 grid;
+    if (!bake_gmm_grid(K, nx, ny, z_base, nzs, grid) ||
+        !with_value<0, 1>(spread, [&](auto sp) {
+            return with_gmm_records(wm, sg, half, K, [&](auto w, auto g, auto k) {
+                hipLaunchKernelGGL((k_bake_gmm_quant<ElemOf<decltype(w)>, decltype(k)::value,
+                                                     decltype(sp)::value != 0>),
+                                   grid, dim3(256), 0, s, w, g, (uint32_t)nx, (uint32_t)ny,
+                                   (uint32_t)z_base, Q, out, psy, psz);
+            });
+        }))
         return hipErrorInvalidValue;
-    return spread ? launch_bake_gmm_quant_s<true>(wm, sg, half, K, (uint32_t)nx, (uint32_t)ny,
-                                                  (uint32_t)z_base, (uint32_t)nzs, Q, out, psy, psz, s)
-                  : launch_bake_gmm_quant_s<false>(wm, sg, half, K, (uint32_t)nx, (uint32_t)ny,
-                                                   (uint32_t)z_base, (uint32_t)nzs, Q, out, psy, psz, s);
-}
-
-template <typename T>
-static hipError_t launch_bake_gmm_t(const T *wm, const T *sg, int K, uint32_t nx, uint32_t ny,
-                                    uint32_t z_base, uint32_t nzs, float *out, uint64_t plane,
-                                    uint64_t psy, uint64_t psz, hipStream_t s) {
-    const uint32_t per_wg = 4u * 64u / (uint32_t)(K / 4);  // voxels of a row per workgroup
-    const dim3 grid((nx + per_wg - 1) / per_wg, ny, nzs), block(256);
-    switch (K) {
-    case 8: hipLaunchKernelGGL((k_bake_gmm<T, 8>), grid, block, 0, s, wm, sg, nx, ny, z_base, out, plane, psy, psz); break;
-    case 16: hipLaunchKernelGGL((k_bake_gmm<T, 16>), grid, block, 0, s, wm, sg, nx, ny, z_base, out, plane, psy, psz); break;
-    case 32: hipLaunchKernelGGL((k_bake_gmm<T, 32>), grid, block, 0, s, wm, sg, nx, ny, z_base, out, plane, psy, psz); break;
-    default: return hipErrorInvalidValue;
-    }
     return hipGetLastError();
 }
 
 hipError_t launch_bake_gmm(const void *wm, const void *sg, bool half, int K, int nx, int ny,
                            int z_base, int nzs, float *out, uint64_t plane, uint64_t psy,
                            uint64_t psz, hipStream_t s) {
-    // (grid y / z: rows and slices; plane_bx: x < 2^16)
-    if (nx <= 0 || ny <= 0 || nzs <= 0 || z_base < 0 || nx > 65535 || ny > 65535 || nzs > 65535)
+    dim3 grid;
+    if (!bake_gmm_grid(K, nx, ny, z_base, nzs, grid) ||
+        !with_gmm_records(wm, sg, half, K, [&](auto w, auto g, auto k) {
+            hipLaunchKernelGGL((k_bake_gmm<ElemOf<decltype(w)>, decltype(k)::value>), grid,
+                               dim3(256), 0, s, w, g, (uint32_t)nx, (uint32_t)ny,
+                               (uint32_t)z_base, out, plane, psy, psz);
+        }))
         return hipErrorInvalidValue;
-    if (half)
-        return launch_bake_gmm_t(static_cast<const _Float16 *>(wm), static_cast<const _Float16 *>(sg),
-                                 K, (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs,
-                                 out, plane, psy, psz, s);
-    return launch_bake_gmm_t(static_cast<const float *>(wm), static_cast<const float *>(sg), K,
-                             (uint32_t)nx, (uint32_t)ny, (uint32_t)z_base, (uint32_t)nzs, out,
-                             plane, psy, psz, s);
+    return hipGetLastError();
 }
 
 // ---- synthetic GMM volume ----

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "vr_device.h"
 #include "vr_plan.h"
 
@@ -31,6 +33,19 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+
+// Host-side dispatch of the launchers, from a runtime value to the template
+// argument of a compiled instance: f(std::integral_constant<int, V>{}) for the V
+// among Vs that v equals, and what f returns (launched); false, nothing called:
+// no instance for v.
+template <int... Vs, typename F>
+inline bool with_value(int v, F &&f) {
+    return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
+}
+
+// the element type behind a typed record pointer such a dispatch hands on
+template <typename P>
+using ElemOf = std::remove_cv_t<std::remove_pointer_t<P>>;
 
 // records an error for vr_last_error() (vr_api.cpp); returns status
 int record_error(int status, const char *msg);

@@ -16,8 +16,6 @@
 #include "vr_internal.h"
 #include "vr_march.h"
 
-#include <type_traits>
-
 namespace vr {
 
 // a corner's record as it is kept between gather and decode: floats, or the
@@ -224,16 +222,8 @@ __device__ __forceinline__ void bake_lin_kernel(const T *vol, const Params &P, c
     put_plane(out, x, blockIdx.y, blockIdx.z, psy, psz, st(r));
 }
 
-// Host-side dispatch of the launchers, from a runtime value to the template
-// argument of a compiled instance: f(std::integral_constant<int, V>{}) for the V
-// among Vs that v equals, and what f returns (launched); false, nothing called:
-// no instance for v.
-template <int... Vs, typename F>
-inline bool with_value(int v, F &&f) {
-    return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
-}
-
-// the bin counts the query kernels are compiled for (no runtime-B instance):
+// Host-side dispatch of the launchers (with_value, vr_internal.h): the bin counts
+// the query kernels are compiled for (no runtime-B instance):
 // f(std::integral_constant<int, B>{})
 template <typename F>
 inline bool with_bins(int nb, F &&f) {
@@ -244,7 +234,7 @@ inline bool with_bins(int nb, F &&f) {
 }
 
 // ... and the records' element type with them: f(v, B), v the volume as
-// const float * or const _Float16 * (ElemOf<decltype(v)>: that type)
+// const float * or const _Float16 * (ElemOf<decltype(v)>, vr_internal.h: that type)
 template <typename F>
 inline bool with_records(const void *vol, bool half, int nb, F &&f) {
     return with_bins(nb, [&](auto B) {
@@ -252,8 +242,6 @@ inline bool with_records(const void *vol, bool half, int nb, F &&f) {
         else f(static_cast<const float *>(vol), B);
     });
 }
-template <typename P>
-using ElemOf = std::remove_cv_t<std::remove_pointer_t<P>>;
 
 // the grid of a bake launch; false: more rows or slices than a grid takes
 inline bool bake_lin_grid(const Params &P, dim3 &grid) {
