@@ -995,6 +995,49 @@ int vr_release_gmm_quantile(void);
 int vr_gmm_quantile_info(vr_extent *dims, const float **d_plane, uint64_t *plane_floats,
                          int *slices_baked);
 
+/* A user-defined transfer function for frames from baked planes (DESIGN.md
+ * section 22).  Every frame is classified through the reference's nine-entry
+ * rainbow (K:2323-2326) unless a table is set here: n RGBA entries, 1 <= n <=
+ * VR_TF_MAX, sampled exactly as the built-in nine are -- linear filter,
+ * normalised coordinate x = (sample - transfer_offset) * transfer_scale clamped
+ * to [0, 1], entry i centred at (i + 1/2) / n, 8-bit fractional weight, indices
+ * clamped to [0, n - 1] -- with every operation a separate float one.  The table's
+ * values are not clamped (the packed pixel saturates, as always); compositing is
+ * unchanged.  A table of the reference's nine entries gives the built-in frames
+ * bit for bit.
+ *
+ * vr_set_transfer_function: n entries of r, g, b, a, copied; rgba == NULL clears
+ * the table (n ignored).  n outside 1 .. VR_TF_MAX or a value that is not finite:
+ * VR_ERR_ARG, the state stays as it was.  Host state only: no device call, so it
+ * works without a GPU; the device copy is made or refreshed by the next frame that
+ * uses it (one synchronisation of the render stream then, nothing extra in later
+ * frames).  The table is the caller's, like the bin weights: it survives new
+ * volumes, vr_convert_f16, vr_release_*, and freeCudaBuffers (which frees only the
+ * device copy); only a NULL call clears it.  It drops no baked plane.
+ * vr_transfer_function: the table (rgba: room for 4 * VR_TF_MAX floats, or NULL)
+ * and its entry count, *n = 0 when the built-in table is in use; either argument
+ * may be NULL.
+ *
+ * While a table is set a frame comes from a baked plane or not at all:
+ *   vr_render / render_kernel, methods 1/2/3 with vr_bake_stats' planes resident,
+ *     4/5/6 with the codec planes resident, 10/11/12 with the query's plane
+ *     resident: k_march_plane_tf on that plane in its x-row bricks, whatever the
+ *     view (vr_last_kernel "k_march_plane_tf<B=1,M=0>"); no plan is consulted and
+ *     no layout copy is made or used;
+ *   method 13 with the crossing plane resident, and vr_render_gmm_baked with
+ *     queryMethod 13: the same kernel with the crossing combine ("<B=1,M=13>");
+ *   vr_render_gmm_baked with queryMethod 1, 2, 10, 11: as the first case;
+ *   everything else -- every per-step march, method 7, methods 8/9/0,
+ *     vr_render_gmm, vr_count_footprint, vr_footprint_bytes,
+ *     vr_gmm_count_footprint(_slab) -- is VR_ERR_UNSUPPORTED: bake first, or clear
+ *     the table.  Nothing falls back to the built-in table.
+ * Tile lists, d_output_f, d_steps and clipped coverage work as in every other
+ * frame.  Tuning key VR_TF_WIDE=1 forces the instance with 64-bit plane indices
+ * (chosen by itself for planes beyond 32-bit indices). */
+#define VR_TF_MAX 256
+int vr_set_transfer_function(const float *rgba, int n);
+int vr_transfer_function(float *rgba, int *n);
+
 /* library version string */
 const char *vr_version(void);
 

@@ -27,6 +27,7 @@ VR_DIST_L1 = 0
 VR_DIST_EMD = 1
 VR_DIST_KS = 2
 VR_QUERY_CROSSING = 13
+VR_TF_MAX = 256  # entries of a user-defined transfer function
 
 
 class VRError(RuntimeError):
@@ -123,6 +124,7 @@ EXPORTS = [
     "vr_release_distance", "vr_distance_info",
     "vr_set_crossing_weights", "vr_crossing_weights", "vr_set_isovalue", "vr_bake_crossing",
     "vr_release_crossing", "vr_crossing_info",
+    "vr_set_transfer_function", "vr_transfer_function",
 ]
 
 _lib = None
@@ -333,6 +335,10 @@ def load() -> ctypes.CDLL:
     L.vr_release_crossing.restype = i32
     L.vr_crossing_info.argtypes = [vp] * 2
     L.vr_crossing_info.restype = i32
+    L.vr_set_transfer_function.argtypes = [vp, i32]
+    L.vr_set_transfer_function.restype = i32
+    L.vr_transfer_function.argtypes = [vp, vp]
+    L.vr_transfer_function.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

@@ -952,6 +952,45 @@ def gmm_quantile_info():
     return (e.width, e.height, e.depth), p.value, n.value, k.value
 
 
+# ------------------- user-defined transfer function
+
+TF_MAX = _lib.VR_TF_MAX
+
+# the built-in table: the reference's nine RGBA entries (K:2323-2326).  Set as a
+# custom table it gives the built-in frames bit for bit.
+REFERENCE_TF = np.array([
+    [0.0, 0.0, 0.0, 0.0], [1.0, 0.0, 0.0, 1.0], [1.0, 0.5, 0.0, 1.0], [1.0, 1.0, 0.0, 1.0],
+    [0.0, 1.0, 0.0, 1.0], [0.0, 1.0, 1.0, 1.0], [0.0, 0.0, 1.0, 1.0], [1.0, 0.0, 1.0, 1.0],
+    [0.0, 0.0, 0.0, 0.0]], dtype=np.float32)
+REFERENCE_TF.setflags(write=False)
+
+
+def set_transfer_function(table) -> None:
+    """Classify frames through `table`, (n, 4) finite floats r, g, b, a with
+    1 <= n <= TF_MAX, sampled as the built-in nine entries are (linear, clamped,
+    8-bit weights; values not clamped); None returns to the built-in table.  Host
+    state only, the caller's like the bin weights: it survives new volumes and
+    freeCudaBuffers and drops no baked plane.  While a table is set frames come from
+    baked planes (bake_stats, bake_weighted / _quantile / _distance / _crossing,
+    render_gmm_baked); everything else raises VRError (VR_ERR_UNSUPPORTED)."""
+    L = _lib.load()
+    if table is None:
+        check(L.vr_set_transfer_function(None, 0))
+        return
+    a = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"a transfer function is (n, 4) RGBA entries, got shape {a.shape}")
+    check(L.vr_set_transfer_function(a.ctypes.data, int(a.shape[0])))
+
+
+def transfer_function():
+    """The table set, an (n, 4) float32 array; None: the built-in table is in use."""
+    t = np.zeros((TF_MAX, 4), np.float32)
+    n = ctypes.c_int()
+    check(_lib.load().vr_transfer_function(t.ctypes.data, ctypes.addressof(n)))
+    return t[:n.value].copy() if n.value else None
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -978,5 +1017,6 @@ __all__ = [
     "set_gmm_range", "clear_gmm_range", "gmm_range", "gmm_phi_table", "bake_gmm_range",
     "release_gmm_range", "gmm_range_info",
     "gmm_quantile_steps", "bake_gmm_quantile", "release_gmm_quantile", "gmm_quantile_info",
+    "TF_MAX", "REFERENCE_TF", "set_transfer_function", "transfer_function",
     "VRError", "PAD",
 ]

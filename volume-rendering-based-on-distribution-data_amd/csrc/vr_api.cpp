@@ -125,6 +125,17 @@ struct State {
     // from method 10's qw; its plane holds F
     vr::BinWeights xw = {};
     int xn = 0;
+    // user-defined transfer function: tf_n RGBA entries
+    // (0: none set, the built-in table), the caller's like the weights above and
+    // tied to no volume.  Host state; tf_dev is its device copy (kTfMax float4,
+    // nullptr: not made), stale while tf_dirty, made and refreshed by the frame
+    // that needs it (tf_upload) from the snapshot tf_up; tf_stream: the stream of the
+    // last upload or frame that touched it
+    float tf[4 * vr::kTfMax] = {0}, tf_up[4 * vr::kTfMax] = {0};
+    int tf_n = 0;
+    float4 *tf_dev = nullptr;
+    bool tf_dirty = false;
+    hipStream_t tf_stream = nullptr;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -1787,6 +1798,85 @@ int launch_query(const RecordQuery &q, const vr_render_desc *desc, vr::Params &P
     return VR_OK;
 }
 
+// ---- frames under a user-defined transfer function ----
+
+// What has no plane march under a custom table is refused, never rendered with the
+// built-in one (a count too: early termination depends on the table).
+int tf_refuse(const char *what) {
+    return fail(VR_ERR_UNSUPPORTED, "%s: a custom transfer function renders baked planes only "
+                                    "(bake the statistic first, or clear the table with "
+                                    "vr_set_transfer_function(NULL, 0))", what);
+}
+
+// The device copy of the table, made or refreshed for the frame about to use it.
+// Frames already queued may still read the old copy: the stream that last read it
+// drains first (the render stream; the device if the stream was changed since).
+// The copy itself is ordered on the render stream, before the frame's launch.
+int tf_upload() {
+    if (!g.tf_dev) {
+        VR_HIP(hipMalloc(&g.tf_dev, sizeof g.tf));
+        g.tf_dirty = true;
+        g.tf_stream = g.stream;
+    }
+    if (g.tf_dirty) {
+        VR_HIP(g.tf_stream == g.stream ? hipStreamSynchronize(g.stream) : hipDeviceSynchronize());
+        // (from a snapshot the setter never writes: the copy may still be in flight
+        // when the table is set again; the drain above has finished the last one)
+        std::memcpy(g.tf_up, g.tf, sizeof g.tf);
+        g.tf_stream = g.stream;
+        VR_HIP(hipMemcpyAsync(g.tf_dev, g.tf_up, sizeof g.tf_up, hipMemcpyHostToDevice, g.stream));
+        g.tf_dirty = false;
+    }
+    return VR_OK;
+}
+
+void release_tf_device() {
+    if (g.tf_dev) (void)hipFree(g.tf_dev);
+    g.tf_dev = nullptr;
+    g.tf_dirty = false;
+}
+
+// A frame of P's grid from `plane` (one float per voxel in x-row bricks of pitches
+// psy / psz) under the table: k_march_plane_tf on the bricks themselves, whatever
+// the view -- no plan, no layout copy.  cross: the plane holds F (method 13).
+int launch_tf_frame(vr::Params &P, uint32_t nslots, const float *plane, uint64_t psy, uint64_t psz,
+                    bool cross) {
+    const int rc = tf_upload();
+    if (rc != VR_OK) return rc;
+    P.nb = 1;
+    P.sy = psy;
+    P.sz = psz;
+    const hipError_t e =
+        vr::launch_march_plane_tf(plane, P, g.tf_dev, g.tf_n, cross, nslots, g.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch(k_march_plane_tf)");
+    g.tf_stream = g.stream;
+    if (P.tile_cost) g.cost_recorded = true;
+    return VR_OK;
+}
+
+// vr_render's frame under the table: the resident baked plane of the method
+// (statistics planes: methods 1/2/3, codec planes: 4/5/6, a record query's plane:
+// 10-13), or a refusal
+int render_tf_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, bool dry) {
+    const int qm = desc->query_method;
+    const State::Planes *pl = nullptr;
+    int k = 0;
+    bool cross = false;
+    if (qm >= 1 && qm <= 3) {
+        pl = &g.stats;
+        k = qm - 1;
+    } else if (qm >= 4 && qm <= 6) {
+        pl = &g.cstats;
+        k = qm - 4;
+    } else if (const RecordQuery *q = record_query(qm)) {
+        pl = &query_plane(qm);
+        cross = q->cross_plane;
+    }
+    if (!pl || !pl->buf) return tf_refuse("vr_render");
+    if (dry) return VR_OK;
+    return launch_tf_frame(P, nslots, pl->buf + (uint64_t)k * pl->floats, pl->sy, pl->sz, cross);
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -1810,6 +1900,7 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     // what a frame costs the issuing thread
     const char *ed = vr::tuning("VR_DRY");
     const bool dry = ed && std::atoi(ed) != 0;
+    if (g.tf_n) return render_tf_frame(desc, P, nslots, dry);
     hipError_t e;
     const int qm = desc->query_method;
     if (is_flex_method(qm)) {
@@ -1918,6 +2009,7 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
+    if (g.tf_n) return tf_refuse("vr_count_footprint");
     if (desc && record_query(desc->query_method))  // no counting instance of their marches
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
@@ -1948,6 +2040,7 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
+    if (g.tf_n) return tf_refuse("vr_footprint_bytes");
     if (desc && record_query(desc->query_method))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
@@ -2408,6 +2501,7 @@ int vr_free_gmm(void) {
 }
 
 int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
+    if (g.tf_n) return tf_refuse("vr_render_gmm");
     vr::Params P;
     uint32_t nblocks = 0;
     int rc = fill_gmm_params(desc, slab, P, nblocks, false);
@@ -2427,6 +2521,7 @@ int64_t vr_gmm_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_slab *slab) {
+    if (g.tf_n) return tf_refuse("vr_gmm_count_footprint");
     vr::Params P;
     uint32_t nblocks = 0;
     int rc = fill_gmm_params(desc, slab, P, nblocks, true);
@@ -2623,6 +2718,8 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
     const float *pl = b.buf + (uint64_t)plane * b.plane;
+    if (g.tf_n)  // a custom transfer function: k_march_plane_tf for every method here
+        return launch_tf_frame(P, nslots, pl, b.sy, b.sz, desc->query_method == VR_QUERY_CROSSING);
     hipError_t e;
     if (desc->query_method == VR_QUERY_CROSSING) {
         // no plan: the one-lane march on the x-row bricks for every view
@@ -2750,6 +2847,7 @@ void freeCudaBuffers(void) {
     release_flex();
     release_all_gmm();
     for (int set = 0; set < State::kGmmSets; set++) release_gmm_set(set);
+    release_tf_device();  // the table itself is the caller's and stays set
 }
 
 void setTextureFilterMode(bool bLinearFilter) { g.linear_filter = bLinearFilter; }
@@ -3023,6 +3121,37 @@ int vr_bake_crossing(void) { return bake_query(*record_query(VR_QUERY_CROSSING))
 int vr_release_crossing(void) { return release_query(VR_QUERY_CROSSING); }
 int vr_crossing_info(const float **d_plane, uint64_t *plane_floats) {
     return query_info(VR_QUERY_CROSSING, d_plane, plane_floats);
+}
+
+// ---------------- user-defined transfer function ----------
+
+static_assert(VR_TF_MAX == vr::kTfMax, "vr.h repeats vr_internal.h's table size");
+
+int vr_set_transfer_function(const float *rgba, int n) {
+    if (!rgba) {  // clear: the built-in table
+        g.tf_n = 0;
+        g.volume_epoch++;  // a tile order learned under the table is not reused
+        return VR_OK;
+    }
+    if (n < 1 || n > VR_TF_MAX)
+        return fail(VR_ERR_ARG, "a transfer function of %d entries (1 .. %d)", n, VR_TF_MAX);
+    for (int i = 0; i < 4 * n; i++)
+        if (!std::isfinite(rgba[i]))
+            return fail(VR_ERR_ARG, "transfer function entry %d, channel %d is not finite", i / 4,
+                        i % 4);
+    float t[4 * VR_TF_MAX] = {0};
+    std::memcpy(t, rgba, (size_t)n * 4 * sizeof(float));  // (rgba may be g.tf itself)
+    std::memcpy(g.tf, t, sizeof g.tf);
+    g.tf_n = n;
+    g.tf_dirty = true;  // uploaded by the next frame that uses it
+    g.volume_epoch++;
+    return VR_OK;
+}
+
+int vr_transfer_function(float *rgba, int *n) {
+    if (rgba && g.tf_n) std::memcpy(rgba, g.tf, (size_t)g.tf_n * 4 * sizeof(float));
+    if (n) *n = g.tf_n;
+    return VR_OK;
 }
 
 int vr_stats_info(const float **d_raw, uint64_t *raw_plane, const float **d_codec,

@@ -36,22 +36,7 @@ struct CrossStat {
     }
 };
 
-// The combine: all float, every operation separate, in
-// corner order (gather8's: x = c & 1, y = c & 2, z = c & 4), nothing clamped,
-// subnormal products kept.  The filter weights of the footprint are not read: the
-// sample is constant inside a cell.  Corners that the clamped footprint makes
-// coincide enter once per fetch.
-struct CrossCombine {
-    __device__ __forceinline__ float operator()(const float (&s)[8], const Foot &) const {
-        float lo = s[0], hi = 1.0f - s[0];
-#pragma unroll
-        for (int c = 1; c < 8; c++) {
-            lo = lo * s[c];
-            hi = hi * (1.0f - s[c]);
-        }
-        return (1.0f - lo) - hi;
-    }
-};
+// (the combine, CrossCombine: vr_query.h, shared with vr_transfer.hip)
 
 // Waves per SIMD the register allocation may assume: VR_LIN_MAXWAVES' caps
 #ifndef VR_CROSS_MAXWAVES

@@ -244,6 +244,17 @@ hipError_t launch_march_cross(const void *vol, bool half, const Params &P, const
 // they fit, 64-bit ones otherwise
 hipError_t launch_march_cross_plane(const float *plane, const Params &P, uint32_t nslots,
                                     hipStream_t s);
+// ---- user-defined transfer function (vr_transfer.hip) ----
+// entries of a table (VR_TF_MAX of include/vr.h); the device copy always holds this many
+constexpr int kTfMax = 256;
+// k_march_plane_tf: k_march_cross_plane's one-lane march over a plane of one float
+// per voxel in 16 x 2 x 1 bricks of pitches P.sy / P.sz (P.nb = 1), classified
+// through the first n (1 .. kTfMax) RGBA entries of the device table (kTfMax
+// float4, staged into LDS) in place of the built-in nine.  cross: the sample is the
+// crossing combine of the 8 corners (M=13), else their trilinear blend (M=0).
+// 32-bit plane indices where they fit and VR_TF_WIDE is unset, 64-bit ones otherwise.
+hipError_t launch_march_plane_tf(const float *plane, const Params &P, const float4 *table, int n,
+                                 bool cross, uint32_t nslots, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,

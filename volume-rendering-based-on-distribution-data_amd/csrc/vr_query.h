@@ -9,7 +9,8 @@
 // What is made of a step's 8 corner statistics is a functor too,
 //     float operator()(const float (&s)[8], const Foot &) const
 // the trilinear blend (Blend8) unless a query says otherwise (method 13: a joint
-// function of the corners, CrossCombine).
+// function of the corners, CrossCombine).  The plane march under a user-defined
+// transfer function (vr_transfer.hip) takes lin_ray and the two functors from here.
 #pragma once
 #include "vr_device.h"
 #include "vr_half.h"
@@ -68,6 +69,23 @@ constexpr int lin_batch() {
 struct Blend8 {
     __device__ __forceinline__ float operator()(const float (&s)[8], const Foot &f) const {
         return blend8(s, f);
+    }
+};
+
+// The combine of the level-crossing query: all float,
+// every operation separate, in corner order (gather8's: x = c & 1, y = c & 2,
+// z = c & 4), nothing clamped, subnormal products kept.  The filter weights of the
+// footprint are not read: the sample is constant inside a cell.  Corners that the
+// clamped footprint makes coincide enter once per fetch.
+struct CrossCombine {
+    __device__ __forceinline__ float operator()(const float (&s)[8], const Foot &) const {
+        float lo = s[0], hi = 1.0f - s[0];
+#pragma unroll
+        for (int c = 1; c < 8; c++) {
+            lo = lo * s[c];
+            hi = hi * (1.0f - s[c]);
+        }
+        return (1.0f - lo) - hi;
     }
 };
 
