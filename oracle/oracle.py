@@ -71,6 +71,8 @@ def lib():
         L.orc_max_threads.restype = ctypes.c_int
         L.orc_set_reading.argtypes = [ctypes.c_int] * 3
         L.orc_set_reading.restype = None
+        L.orc_set_stat_nudge.argtypes = [ctypes.c_int] * 2
+        L.orc_set_stat_nudge.restype = None
         L.orc_synth_fill.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_uint64, fp, ctypes.c_int]
         L.orc_flex_corner.argtypes = [ctypes.POINTER(Flex), ctypes.c_int, ctypes.c_int,
@@ -203,8 +205,19 @@ def set_reading(w_trunc=0, rsqrt_ulps=0, log_ulps=0) -> None:
     """Parity-margin study only (tools/parity_margin.py): render with another
     reading of what the reference leaves open -- texture weights truncated
     (K:601/619/683), rsqrtf moved by ulps (K:295), per-bin logf moved by ulps
-    (K:766).  set_reading() restores the canonical reading."""
+    (K:766).  set_reading() restores the canonical reading, the statistic nudge
+    (set_stat_nudge) included."""
     lib().orc_set_reading(int(w_trunc), int(rsqrt_ulps), int(log_ulps))
+    if not (w_trunc or rsqrt_ulps or log_ulps):
+        lib().orc_set_stat_nudge(0, 0)
+
+
+def set_stat_nudge(ulps=0, corner_mask=0) -> None:
+    """Sensitivity study of the bit-parity scenes only (tests/magnify.py): the
+    decoded statistic of the masked corners of every sample (bit j = corner j, x
+    fastest) moved by `ulps` before the blend, in the histogram, codec, method-7
+    and GMM marches.  set_stat_nudge() or set_reading() turns it off."""
+    lib().orc_set_stat_nudge(int(ulps), int(corner_mask))
 
 
 def max_threads() -> int:

@@ -67,6 +67,22 @@ static inline float ulp_step(float x, int k) {
     return x;
 }
 
+/* Statistic nudge, for the sensitivity study of the bit-parity scenes only
+ * (orc_set_stat_nudge, tests/magnify.py): the decoded
+ * statistic of the masked corners of every sample (bit j = corner j, x fastest,
+ * then y, then z) moved this many ulps before the blend -- what a decode that
+ * is wrong in its last bit for one corner role would render.  0 / 0 = off. */
+static int g_nudge_ulps = 0, g_nudge_mask = 0;
+
+void orc_set_stat_nudge(int ulps, int corner_mask) {
+    g_nudge_ulps = ulps;
+    g_nudge_mask = corner_mask & 0xff;
+}
+
+static inline float nudge_stat(float s, int corner) {
+    return (g_nudge_ulps && ((g_nudge_mask >> corner) & 1)) ? ulp_step(s, g_nudge_ulps) : s;
+}
+
 /* rsqrtf(dot(v, v)) of normalize (K:295) */
 static inline float rsqrt_read(float x) {
     const float r = 1.0f / sqrtf(x);
@@ -241,30 +257,36 @@ void orc_codec_decode(const orc_codec *c, int nbins, size_t vidx, float *dec) {
 
 /* statistics of a decoded codec record, K:837-868: the bin centre is used in
  * both mean and variance (unlike K:750-755) */
-static void codec_stats3(const orc_codec *c, int nbins, float enorm, size_t vidx, float out[3]) {
+static void codec_stats3(const orc_codec *c, int nbins, float enorm, size_t vidx, int want,
+                         float out[3]) {
     float dec[256];
     orc_codec_decode(c, nbins, vidx, dec);
     const float bw = bin_width(nbins);
     float mean = raw_mean(dec, nbins);
     float var = 0.0f;
-    for (int i = 0; i < nbins; i++) {
-        double d = ((double)(bw * (float)i) + (double)bw / 2.0) - (double)mean;
-        var = (float)((double)var + (double)dec[i] * d * d);
+    if (want & 2) {
+        for (int i = 0; i < nbins; i++) {
+            double d = ((double)(bw * (float)i) + (double)bw / 2.0) - (double)mean;
+            var = (float)((double)var + (double)dec[i] * d * d);
+        }
     }
     out[0] = (float)((double)mean / 0.0217);
     out[1] = (float)((double)var / 0.000021);
     float ent = 0.0f;
-    for (int i = 0; i < nbins; i++) {
-        float pr = dec[i];
-        double t = pr <= 0 ? 0.0 : ((double)logf_bin(pr) / LN2_D);
-        ent = (float)((double)ent + (double)pr * t);
+    if (want & 4) {
+        for (int i = 0; i < nbins; i++) {
+            float pr = dec[i];
+            double t = pr <= 0 ? 0.0 : ((double)logf_bin(pr) / LN2_D);
+            ent = (float)((double)ent + (double)pr * t);
+        }
+        ent = -ent;
+        ent = ent / enorm;
     }
-    ent = -ent;
-    out[2] = ent / enorm;
+    out[2] = ent;
 }
 
 void orc_codec_stats(const orc_codec *c, int nbins, size_t vidx, float out[3]) {
-    codec_stats3(c, nbins, entropy_norm(nbins), vidx, out);
+    codec_stats3(c, nbins, entropy_norm(nbins), vidx, 7, out);
 }
 
 /* methods 1/2/3: tex3D(originalQueryTex, p) with hardware trilinear (K:601, 619,
@@ -291,9 +313,11 @@ static float sample_stat(const vol_t *v, f3 pos, int comp) {
         for (int j = 0; j < 8; j++) {
             size_t idx = ((size_t)zs[j >> 2] * (size_t)v->ny + (size_t)ys[(j >> 1) & 1]) *
                              (size_t)v->nx + (size_t)xs[j & 1];
-            codec_stats3(v->codec, v->nb, v->enorm, idx, s[j]);
+            /* only the sampled statistic is read below */
+            codec_stats3(v->codec, v->nb, v->enorm, idx, 1 << (comp - 3), s[j]);
         }
         comp -= 3;
+        for (int j = 0; j < 8; j++) s[j][comp] = nudge_stat(s[j][comp], j);
         float c00 = lerpq(s[0][comp], s[1][comp], ax);
         float c10 = lerpq(s[2][comp], s[3][comp], ax);
         float c01 = lerpq(s[4][comp], s[5][comp], ax);
@@ -311,6 +335,7 @@ static float sample_stat(const vol_t *v, f3 pos, int comp) {
     stats3(rec_at(v, x1, y0, z1), v->nb, v->enorm, want, s[5]);
     stats3(rec_at(v, x0, y1, z1), v->nb, v->enorm, want, s[6]);
     stats3(rec_at(v, x1, y1, z1), v->nb, v->enorm, want, s[7]);
+    for (int j = 0; j < 8; j++) s[j][comp] = nudge_stat(s[j][comp], j);
     float c00 = lerpq(s[0][comp], s[1][comp], ax);
     float c10 = lerpq(s[2][comp], s[3][comp], ax);
     float c01 = lerpq(s[4][comp], s[5][comp], ax);
@@ -378,7 +403,7 @@ static void m7_refresh(const vol_t *v, const int N[3], f3 pos, m7_t *m) {
         int ix = point_axis(m->ip[j].x, v->nx);
         int iy = point_axis(m->ip[j].y, v->ny);
         int iz = point_axis(m->ip[j].z, v->nz);
-        m->mean[j] = raw_mean(rec_at(v, ix, iy, iz), v->nb);
+        m->mean[j] = nudge_stat(raw_mean(rec_at(v, ix, iy, iz), v->nb), j);
     }
 }
 
@@ -1128,6 +1153,7 @@ static int gmm_march(const orc_gmm *v, const orc_gmm_proc *proc, const orc_rende
             } else {
                 sv[j] = orc_gmm_stat(gmm_wm(v, X, Y, Z), gmm_sg(v, X, Y, Z), v->K, p->query_method);
             }
+            sv[j] = nudge_stat(sv[j], j);
         }
         float c00 = lerpq(sv[0], sv[1], ax), c10 = lerpq(sv[2], sv[3], ax);
         float c01 = lerpq(sv[4], sv[5], ax), c11 = lerpq(sv[6], sv[7], ax);
@@ -1181,6 +1207,12 @@ int64_t orc_render_gmm(const orc_gmm *v, const orc_render_params *p, int z_lo, i
     const uint64_t n = rays_in ? (uint64_t)n_in : (uint64_t)p->width * (uint64_t)p->height;
     int64_t samples = 0;
     uint32_t k_out = 0;
+    /* a whole-volume render from the camera lists no alive rays (gmm_march returns
+     * 1 only inside a slab), so its pixels are independent; a slab keeps the list's
+     * order and runs serially */
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : samples) if (!slab && !rays_in)
+#endif
     for (uint64_t i = 0; i < n; i++) {
         orc_gmm_ray s;
         memset(&s, 0, sizeof s);

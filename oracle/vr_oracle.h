@@ -136,6 +136,12 @@ int orc_max_threads(void);
  * and logf (vr_oracle.c g_w_trunc / g_rsqrt_ulps / g_log_ulps); (0, 0, 0) =
  * the canonical reading.  Not thread-safe: set it before a render. */
 void orc_set_reading(int w_trunc, int rsqrt_ulps, int log_ulps);
+/* sensitivity study of the bit-parity scenes only (tests/magnify.py): the decoded
+ * statistic of the masked corners of every sample (bit j = corner j: x fastest,
+ * then y, then z; methods 1-6, method 7's corner means, the GMM march) moved by
+ * `ulps` before the blend.  (0, 0) = off, the canonical reading.  Not
+ * thread-safe: set it before a render. */
+void orc_set_stat_nudge(int ulps, int corner_mask);
 void orc_synth_fill(int nx, int ny, int nz, int nbins, uint64_t seed, float *vol,
                     int nthreads);
 

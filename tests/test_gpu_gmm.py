@@ -3,7 +3,8 @@ oracle, through the C-ABI: whole-volume renders, slab chains with only each
 slab's slices resident, the on-device generator, the footprint count and the
 error paths.  Bar: packed RGBA8 and samples per pixel identical, float RGBA
 within 1e-4 (the north star's tolerance; the decode order is fixed, so the
-results are in fact bit-identical)."""
+results are in fact bit-identical: tests/test_gpu_bitparity.py::test_gmm asserts
+that, word for word, on frames that magnify the decode)."""
 import os
 
 import numpy as np

@@ -76,3 +76,15 @@ def test_canonical_reading_is_restored(orc):
     c = orc.render(vol, p)[0]
     assert np.array_equal(a, c)
     assert not np.array_equal(a, b)
+    # the statistic nudge (tests/magnify.py) is part of the reading: every corner
+    # moved by 256 ulps is another float frame, and set_reading() clears it too
+    af = orc.render(vol, p)[1]
+    orc.set_stat_nudge(256, 0xFF)
+    d = orc.render(vol, p)[1]
+    orc.set_reading()
+    e = orc.render(vol, p)[1]
+    assert not np.array_equal(af, d)
+    assert np.array_equal(af.view(np.uint32), e.view(np.uint32))
+    orc.set_stat_nudge(256, 0xFF)
+    orc.set_stat_nudge()
+    assert np.array_equal(af.view(np.uint32), orc.render(vol, p)[1].view(np.uint32))
