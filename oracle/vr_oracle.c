@@ -19,6 +19,11 @@
  *    [0,1] first, which gives the same texels as index clamping and a
  *    defined answer for NaN);  1-D/3-D linear blends are
  *    (1-a)*t0 + a*t1, x first, then y, then z.
+ *
+ * tests/test_reference_text.py checks these rules: it compares this file word
+ * for word with the reference's own kernel text compiled as host C++ with
+ * -ffp-contract=off (oracle/ref/build_ref.py), whose shim headers take the same
+ * readings of rsqrtf, log(float) and the texture fetch.
  */
 #include "vr_oracle.h"
 

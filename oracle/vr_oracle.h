@@ -6,11 +6,13 @@
  * in __graft_entry__.py and bench.py's cpu_baseline leg load it, and only as
  * the checker / the reported CPU baseline.
  *
- * Parity status: the reference (CUDA 5.0 + texture hardware) cannot be built or
- * run here and ships no golden image.  This restatement is
- * pinned by analytic known-answer tests (tests/test_oracle.py) and by the
- * committed fixtures in tests/golden/; against real NVIDIA output it is
- * "parity unpinned" (see DESIGN.md section 3).
+ * Parity status: the reference (CUDA 5.0 + texture hardware) cannot be run here
+ * and ships no golden image.  This restatement is pinned word
+ * for word to the reference's own kernel text compiled for the CPU
+ * (oracle/ref/, tests/test_reference_text.py), by analytic known-answer tests
+ * (tests/test_oracle.py) and by the committed fixtures in tests/golden/.  What
+ * only NVIDIA hardware or nvcc can settle (texture-unit rounding, logf, rsqrtf,
+ * contraction) stays open.
  */
 #ifndef VR_ORACLE_H
 #define VR_ORACLE_H
