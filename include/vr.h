@@ -1033,10 +1033,85 @@ int vr_gmm_quantile_info(vr_extent *dims, const float **d_plane, uint64_t *plane
  *     the table.  Nothing falls back to the built-in table.
  * Tile lists, d_output_f, d_steps and clipped coverage work as in every other
  * frame.  Tuning key VR_TF_WIDE=1 forces the instance with 64-bit plane indices
- * (chosen by itself for planes beyond 32-bit indices). */
+ * (chosen by itself for planes beyond 32-bit indices).
+ *
+ * At most one of this table and the 2-D table below is set: a successful
+ * vr_set_transfer_function(non-NULL) clears the 2-D table; a NULL call clears only
+ * this one. */
 #define VR_TF_MAX 256
 int vr_set_transfer_function(const float *rgba, int n);
 int vr_transfer_function(float *rgba, int *n);
+
+/* A 2-D transfer function over two baked planes of one volume (DESIGN.md section
+ * 23): colour by one statistic, opacity by another, inside one march.  The table
+ * has nu x nv RGBA float entries, entry (i, j) at rgba[4 * (j * nu + i)] (u
+ * fastest), 1 <= nu, nv <= 256 and nu * nv <= VR_TF2_MAX.  At every sample the
+ * march forms two numbers from the same footprint: su from the plane of the
+ * frame's query_method ("u"), sv from the plane of method_v ("v"), each the
+ * trilinear blend of its eight corners (method 13: the crossing combine of them,
+ * as in the one-plane frames).  Then, with lin_axis (linear filter, coordinate
+ * clamped to [0, 1], NaN as 0, entry i centred at (i + 1/2) / n, 8-bit weight,
+ * indices clamped) and lerpq(p, q, t) = (1 - t) * p + t * q:
+ *
+ *   xu = (su - transfer_offset) * transfer_scale ;  lin_axis(xu, nu, i0, i1, a)
+ *   xv = (sv - v_offset)        * v_scale        ;  lin_axis(xv, nv, j0, j1, b)
+ *   for c in r, g, b, a:
+ *       r0    = lerpq(tab[j0][i0].c, tab[j0][i1].c, a)
+ *       r1    = lerpq(tab[j1][i0].c, tab[j1][i1].c, a)
+ *       col.c = lerpq(r0, r1, b)
+ *
+ * every operation a separate float one, nothing in the table clamped, subnormals
+ * kept; compositing is unchanged (col.a *= density, premultiply, over, exit at
+ * 0.95).  numpy float32 restates it bit for bit.
+ *
+ * Collapse to the 1-D table: lerpq(r, r, b) is not r in general, but it is when
+ * every table value is m / 256 with an integer 0 <= m <= 256 (a and b are multiples
+ * of 2^-8, so r0 is a multiple of 2^-16 no larger than 1 and both products of the
+ * second lerp are exact).  A table whose rows all hold the same such 8-bit 1-D
+ * table, with any nv including 1, therefore gives the one-plane frame of
+ * vr_set_transfer_function with that 1-D table bit for bit, whatever plane v is;
+ * with the reference's nine entries as rows it gives the built-in frames.  The
+ * property holds for 8-bit values only: rows of arbitrary floats differ from the
+ * 1-D frame in the last bit of some samples.
+ *
+ * vr_set_transfer_function_2d: nu * nv entries, copied; rgba == NULL clears the
+ * table (the other arguments are not read).  nu or nv outside 1 .. 256, nu * nv >
+ * VR_TF2_MAX, a table value, v_offset or v_scale that is not finite, or a method_v
+ * outside {1, 2, 3, 4, 5, 6, 10, 11, 12, 13}: VR_ERR_ARG, the state stays as it
+ * was.  Host state only, kept exactly as the 1-D table is: no device call (works
+ * without a GPU), uploaded by the next frame that uses it into a device buffer of
+ * its own, the caller's (survives new volumes, vr_convert_f16, vr_release_* and
+ * freeCudaBuffers, which frees only the device copy), drops no baked plane.
+ * At most one of the two tables is set: a successful
+ * vr_set_transfer_function_2d(non-NULL) clears the 1-D table; a NULL call clears
+ * only the 2-D one.
+ * vr_transfer_function_2d: the table (rgba: room for 4 * VR_TF2_MAX floats, or
+ * NULL), its shape and the v axis; *nu = *nv = 0 when none is set (the other
+ * outputs are then left alone); every argument may be NULL.
+ *
+ * While a 2-D table is set:
+ *   vr_render / render_kernel with query_method u: u and method_v both from
+ *     {1, 2, 3, 10, 11, 12, 13} (vr_bake_stats' planes and the record queries'
+ *     planes) or both from {4, 5, 6} (the codec planes), each the plane the 1-D
+ *     route takes, both resident: k_march_tf2 on the two planes in their x-row
+ *     bricks, whatever the view (vr_last_kernel "k_march_tf2<B=2,M=c>" with
+ *     c = (u is 13) + 2 * (method_v is 13)); u == method_v is allowed;
+ *   vr_render_gmm_baked with u and method_v from {1, 2, 10, 11, 13} in their GMM
+ *     meaning (10 and 13 both read the range plane, 13 combined), every plane set
+ *     used complete (else VR_ERR_STATE, as without a table) and of the same
+ *     dimensions (else VR_ERR_STATE);
+ *   a plane that is not resident, or a u / method_v pair of different families:
+ *     VR_ERR_UNSUPPORTED with the 1-D table's message (bake first, or clear);
+ *   everything else is VR_ERR_UNSUPPORTED exactly as under a 1-D table.  Nothing
+ *     falls back to the built-in table or to the 1-D route.
+ * Tile lists, d_output_f, d_steps, clipped coverage and VR_TF_WIDE work as under
+ * the 1-D table.  VR_TF2_MAX is 1024 because the table is staged in LDS as float4
+ * (16 KiB a workgroup). */
+#define VR_TF2_MAX 1024
+int vr_set_transfer_function_2d(const float *rgba, int nu, int nv, int method_v, float v_offset,
+                                float v_scale);
+int vr_transfer_function_2d(float *rgba, int *nu, int *nv, int *method_v, float *v_offset,
+                            float *v_scale);
 
 /* library version string */
 const char *vr_version(void);

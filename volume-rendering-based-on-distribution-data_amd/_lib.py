@@ -28,6 +28,7 @@ VR_DIST_EMD = 1
 VR_DIST_KS = 2
 VR_QUERY_CROSSING = 13
 VR_TF_MAX = 256  # entries of a user-defined transfer function
+VR_TF2_MAX = 1024  # entries (nu * nv) of a 2-D one
 
 
 class VRError(RuntimeError):
@@ -125,6 +126,7 @@ EXPORTS = [
     "vr_set_crossing_weights", "vr_crossing_weights", "vr_set_isovalue", "vr_bake_crossing",
     "vr_release_crossing", "vr_crossing_info",
     "vr_set_transfer_function", "vr_transfer_function",
+    "vr_set_transfer_function_2d", "vr_transfer_function_2d",
 ]
 
 _lib = None
@@ -339,6 +341,10 @@ def load() -> ctypes.CDLL:
     L.vr_set_transfer_function.restype = i32
     L.vr_transfer_function.argtypes = [vp, vp]
     L.vr_transfer_function.restype = i32
+    L.vr_set_transfer_function_2d.argtypes = [vp, i32, i32, i32, ctypes.c_float, ctypes.c_float]
+    L.vr_set_transfer_function_2d.restype = i32
+    L.vr_transfer_function_2d.argtypes = [vp] * 6
+    L.vr_transfer_function_2d.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

@@ -991,6 +991,50 @@ def transfer_function():
     return t[:n.value].copy() if n.value else None
 
 
+# ------------- 2-D transfer function over two planes
+
+TF2_MAX = _lib.VR_TF2_MAX
+
+
+def set_transfer_function_2d(table, method_v=None, v_offset: float = 0.0,
+                             v_scale: float = 1.0) -> None:
+    """Classify frames through `table`, (nv, nu, 4) finite floats r, g, b, a with
+    1 <= nu, nv <= 256 and nu * nv <= TF2_MAX, looked up bilinearly at
+    ((su - transfer_offset) * transfer_scale, (sv - v_offset) * v_scale): su the
+    sample of the frame's query_method's plane, sv that of method_v's plane, both
+    from one footprint.  None clears it (the other arguments are not read).  Host
+    state of the caller's, kept as set_transfer_function's is; setting one of the
+    two tables clears the other.  While it is set frames come from two resident
+    baked planes of one family (1/2/3/10-13, or the codec's 4/5/6; render_gmm_baked:
+    1, 2, 10, 11, 13); everything else raises VRError (VR_ERR_UNSUPPORTED)."""
+    L = _lib.load()
+    if table is None:
+        check(L.vr_set_transfer_function_2d(None, 0, 0, 0, 0.0, 1.0))
+        return
+    a = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"a 2-D transfer function is (nv, nu, 4) RGBA entries, got shape {a.shape}")
+    if method_v is None:
+        raise ValueError("method_v: the query method whose plane is the table's v axis")
+    check(L.vr_set_transfer_function_2d(a.ctypes.data, int(a.shape[1]), int(a.shape[0]),
+                                        int(method_v), float(v_offset), float(v_scale)))
+
+
+def transfer_function_2d():
+    """(table (nv, nu, 4) float32, method_v, v_offset, v_scale) of the 2-D table set;
+    None: none is set."""
+    t = np.zeros(4 * TF2_MAX, np.float32)
+    nu, nv, mv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    off, scale = ctypes.c_float(), ctypes.c_float()
+    check(_lib.load().vr_transfer_function_2d(
+        t.ctypes.data, ctypes.addressof(nu), ctypes.addressof(nv), ctypes.addressof(mv),
+        ctypes.addressof(off), ctypes.addressof(scale)))
+    if not nu.value:
+        return None
+    return (t[:4 * nu.value * nv.value].reshape(nv.value, nu.value, 4).copy(), mv.value,
+            off.value, scale.value)
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -1018,5 +1062,6 @@ __all__ = [
     "release_gmm_range", "gmm_range_info",
     "gmm_quantile_steps", "bake_gmm_quantile", "release_gmm_quantile", "gmm_quantile_info",
     "TF_MAX", "REFERENCE_TF", "set_transfer_function", "transfer_function",
+    "TF2_MAX", "set_transfer_function_2d", "transfer_function_2d",
     "VRError", "PAD",
 ]

@@ -136,6 +136,17 @@ struct State {
     float4 *tf_dev = nullptr;
     bool tf_dirty = false;
     hipStream_t tf_stream = nullptr;
+    // 2-D transfer function over two planes: tf2_nu x tf2_nv
+    // RGBA entries, u fastest (0 x 0: none set), classified over the frame's plane
+    // (u) and the plane of method tf2_mv (v) at (sv - tf2_voff) * tf2_vscale.  At
+    // most one of tf_n and tf2_nu is non-zero.  Host state with a device copy of
+    // its own (kTf2Max float4), kept exactly as the 1-D table's above
+    float tf2[4 * vr::kTf2Max] = {0}, tf2_up[4 * vr::kTf2Max] = {0};
+    int tf2_nu = 0, tf2_nv = 0, tf2_mv = 0;
+    float tf2_voff = 0.0f, tf2_vscale = 1.0f;
+    float4 *tf2_dev = nullptr;
+    bool tf2_dirty = false;
+    hipStream_t tf2_stream = nullptr;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -1805,35 +1816,53 @@ int launch_query(const RecordQuery &q, const vr_render_desc *desc, vr::Params &P
 int tf_refuse(const char *what) {
     return fail(VR_ERR_UNSUPPORTED, "%s: a custom transfer function renders baked planes only "
                                     "(bake the statistic first, or clear the table with "
-                                    "vr_set_transfer_function(NULL, 0))", what);
+                                    "%s)", what,
+                g.tf2_nu ? "vr_set_transfer_function_2d(NULL, 0, 0, 0, 0, 0)"
+                         : "vr_set_transfer_function(NULL, 0)");
 }
+
+// a 1-D or a 2-D table is set (at most one is)
+bool tf_set() { return g.tf_n || g.tf2_nu; }
 
 // The device copy of the table, made or refreshed for the frame about to use it.
 // Frames already queued may still read the old copy: the stream that last read it
 // drains first (the render stream; the device if the stream was changed since).
 // The copy itself is ordered on the render stream, before the frame's launch.
-int tf_upload() {
-    if (!g.tf_dev) {
-        VR_HIP(hipMalloc(&g.tf_dev, sizeof g.tf));
-        g.tf_dirty = true;
-        g.tf_stream = g.stream;
+int table_upload(float4 *&dev, bool &dirty, hipStream_t &last, const float *host, float *snap,
+                 size_t bytes) {
+    if (!dev) {
+        VR_HIP(hipMalloc(&dev, bytes));
+        dirty = true;
+        last = g.stream;
     }
-    if (g.tf_dirty) {
-        VR_HIP(g.tf_stream == g.stream ? hipStreamSynchronize(g.stream) : hipDeviceSynchronize());
+    if (dirty) {
+        VR_HIP(last == g.stream ? hipStreamSynchronize(g.stream) : hipDeviceSynchronize());
         // (from a snapshot the setter never writes: the copy may still be in flight
         // when the table is set again; the drain above has finished the last one)
-        std::memcpy(g.tf_up, g.tf, sizeof g.tf);
-        g.tf_stream = g.stream;
-        VR_HIP(hipMemcpyAsync(g.tf_dev, g.tf_up, sizeof g.tf_up, hipMemcpyHostToDevice, g.stream));
-        g.tf_dirty = false;
+        std::memcpy(snap, host, bytes);
+        last = g.stream;
+        VR_HIP(hipMemcpyAsync(dev, snap, bytes, hipMemcpyHostToDevice, g.stream));
+        dirty = false;
     }
     return VR_OK;
+}
+
+int tf_upload() {
+    return table_upload(g.tf_dev, g.tf_dirty, g.tf_stream, g.tf, g.tf_up, sizeof g.tf);
+}
+
+// (the 2-D table's copy, a buffer of its own: section 23)
+int tf2_upload() {
+    return table_upload(g.tf2_dev, g.tf2_dirty, g.tf2_stream, g.tf2, g.tf2_up, sizeof g.tf2);
 }
 
 void release_tf_device() {
     if (g.tf_dev) (void)hipFree(g.tf_dev);
     g.tf_dev = nullptr;
     g.tf_dirty = false;
+    if (g.tf2_dev) (void)hipFree(g.tf2_dev);
+    g.tf2_dev = nullptr;
+    g.tf2_dirty = false;
 }
 
 // A frame of P's grid from `plane` (one float per voxel in x-row bricks of pitches
@@ -1857,24 +1886,71 @@ int launch_tf_frame(vr::Params &P, uint32_t nslots, const float *plane, uint64_t
 // vr_render's frame under the table: the resident baked plane of the method
 // (statistics planes: methods 1/2/3, codec planes: 4/5/6, a record query's plane:
 // 10-13), or a refusal
-int render_tf_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, bool dry) {
-    const int qm = desc->query_method;
+// The baked plane a table frame of method qm reads.  family: 0 the record volume's
+// planes (1/2/3, 10-13), 1 the codec planes (4/5/6), -1 no plane march
+struct TfPlane {
     const State::Planes *pl = nullptr;
-    int k = 0;
+    int k = 0, family = -1;
     bool cross = false;
+    const float *ptr() const { return pl->buf + (uint64_t)k * pl->floats; }
+};
+
+TfPlane tf_plane(int qm) {
+    TfPlane t;
     if (qm >= 1 && qm <= 3) {
-        pl = &g.stats;
-        k = qm - 1;
+        t.pl = &g.stats;
+        t.k = qm - 1;
+        t.family = 0;
     } else if (qm >= 4 && qm <= 6) {
-        pl = &g.cstats;
-        k = qm - 4;
+        t.pl = &g.cstats;
+        t.k = qm - 4;
+        t.family = 1;
     } else if (const RecordQuery *q = record_query(qm)) {
-        pl = &query_plane(qm);
-        cross = q->cross_plane;
+        t.pl = &query_plane(qm);
+        t.cross = q->cross_plane;
+        t.family = 0;
     }
-    if (!pl || !pl->buf) return tf_refuse("vr_render");
+    return t;
+}
+
+int render_tf_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, bool dry) {
+    const TfPlane u = tf_plane(desc->query_method);
+    if (!u.pl || !u.pl->buf) return tf_refuse("vr_render");
     if (dry) return VR_OK;
-    return launch_tf_frame(P, nslots, pl->buf + (uint64_t)k * pl->floats, pl->sy, pl->sz, cross);
+    return launch_tf_frame(P, nslots, u.ptr(), u.pl->sy, u.pl->sz, u.cross);
+}
+
+// ---- frames under a 2-D transfer function ----
+
+// A frame of P's grid from the planes pu / pv of one volume (both in x-row bricks
+// of pitches psy / psz) under the 2-D table: k_march_tf2 on the bricks themselves.
+int launch_tf2_frame(vr::Params &P, uint32_t nslots, const float *pu, const float *pv, uint64_t psy,
+                     uint64_t psz, bool cu, bool cv) {
+    const int rc = tf2_upload();
+    if (rc != VR_OK) return rc;
+    P.nb = 1;
+    P.sy = psy;
+    P.sz = psz;
+    const hipError_t e = vr::launch_march_tf2(pu, pv, P, g.tf2_dev, g.tf2_nu, g.tf2_nv, g.tf2_voff,
+                                              g.tf2_vscale, cu, cv, nslots, g.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch(k_march_tf2)");
+    g.tf2_stream = g.stream;
+    if (P.tile_cost) g.cost_recorded = true;
+    return VR_OK;
+}
+
+// vr_render's frame under the 2-D table: the planes of the frame's method (u) and
+// of the table's second method (v), both resident and of one family, or a refusal
+int render_tf2_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, bool dry) {
+    const TfPlane u = tf_plane(desc->query_method), v = tf_plane(g.tf2_mv);
+    if (!u.pl || !v.pl || u.family != v.family || !u.pl->buf || !v.pl->buf)
+        return tf_refuse("vr_render");
+    // (planes of one volume share one brick layout; anything else is a bug here)
+    if (u.pl->floats != v.pl->floats || u.pl->sy != v.pl->sy || u.pl->sz != v.pl->sz)
+        return fail(VR_ERR_STATE, "the planes of methods %d and %d differ in size or pitches",
+                    desc->query_method, g.tf2_mv);
+    if (dry) return VR_OK;
+    return launch_tf2_frame(P, nslots, u.ptr(), v.ptr(), u.pl->sy, u.pl->sz, u.cross, v.cross);
 }
 
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
@@ -1901,6 +1977,7 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     const char *ed = vr::tuning("VR_DRY");
     const bool dry = ed && std::atoi(ed) != 0;
     if (g.tf_n) return render_tf_frame(desc, P, nslots, dry);
+    if (g.tf2_nu) return render_tf2_frame(desc, P, nslots, dry);
     hipError_t e;
     const int qm = desc->query_method;
     if (is_flex_method(qm)) {
@@ -2009,7 +2086,7 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
-    if (g.tf_n) return tf_refuse("vr_count_footprint");
+    if (tf_set()) return tf_refuse("vr_count_footprint");
     if (desc && record_query(desc->query_method))  // no counting instance of their marches
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
@@ -2040,7 +2117,7 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
-    if (g.tf_n) return tf_refuse("vr_footprint_bytes");
+    if (tf_set()) return tf_refuse("vr_footprint_bytes");
     if (desc && record_query(desc->query_method))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
@@ -2501,7 +2578,7 @@ int vr_free_gmm(void) {
 }
 
 int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
-    if (g.tf_n) return tf_refuse("vr_render_gmm");
+    if (tf_set()) return tf_refuse("vr_render_gmm");
     vr::Params P;
     uint32_t nblocks = 0;
     int rc = fill_gmm_params(desc, slab, P, nblocks, false);
@@ -2521,7 +2598,7 @@ int64_t vr_gmm_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_slab *slab) {
-    if (g.tf_n) return tf_refuse("vr_gmm_count_footprint");
+    if (tf_set()) return tf_refuse("vr_gmm_count_footprint");
     vr::Params P;
     uint32_t nblocks = 0;
     int rc = fill_gmm_params(desc, slab, P, nblocks, true);
@@ -2707,9 +2784,25 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     const int plane = set == State::kGmmStats ? desc->query_method - 1 : 0;
     const GmmPlaneSet &ps = kGmmPlaneSets[set];
     const State::GmmStats &b = g.gplanes[set];
+    // (under a 2-D table a plane that is not resident is the table's refusal)
+    if (!b.buf && g.tf2_nu) return tf_refuse("vr_render_gmm_baked");
     if (!b.buf) return fail(VR_ERR_STATE, "no baked GMM %s (%s first)", ps.planes, ps.bake);
     if (b.nbaked != b.nz)
         return fail(VR_ERR_STATE, "%d of the GMM planes' %d slices are baked", b.nbaked, b.nz);
+    // a 2-D table: the v plane, in the methods' GMM meaning, complete and of u's shape
+    const float *pv = nullptr;
+    if (g.tf2_nu) {
+        const int vset = gmm_plane_set(g.tf2_mv);
+        if (vset < 0) return tf_refuse("vr_render_gmm_baked");  // (a codec method: no GMM plane)
+        const State::GmmStats &c = g.gplanes[vset];
+        if (!c.buf) return tf_refuse("vr_render_gmm_baked");
+        if (c.nbaked != c.nz)
+            return fail(VR_ERR_STATE, "%d of the GMM planes' %d slices are baked", c.nbaked, c.nz);
+        if (c.nx != b.nx || c.ny != b.ny || c.nz != b.nz || c.sy != b.sy || c.sz != b.sz)
+            return fail(VR_ERR_STATE, "the GMM planes of methods %d and %d hold volumes of "
+                        "different dimensions", desc->query_method, g.tf2_mv);
+        pv = c.buf + (vset == State::kGmmStats ? (uint64_t)(g.tf2_mv - 1) * c.plane : 0);
+    }
     vr::Params P;
     uint32_t nslots = 0;
     const FrameVol v = {b.nx, b.ny, b.nz, 1, b.sy, b.sz};
@@ -2720,6 +2813,10 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     const float *pl = b.buf + (uint64_t)plane * b.plane;
     if (g.tf_n)  // a custom transfer function: k_march_plane_tf for every method here
         return launch_tf_frame(P, nslots, pl, b.sy, b.sz, desc->query_method == VR_QUERY_CROSSING);
+    if (g.tf2_nu)  // a 2-D one: k_march_tf2 on the two planes
+        return launch_tf2_frame(P, nslots, pl, pv, b.sy, b.sz,
+                                desc->query_method == VR_QUERY_CROSSING,
+                                g.tf2_mv == VR_QUERY_CROSSING);
     hipError_t e;
     if (desc->query_method == VR_QUERY_CROSSING) {
         // no plan: the one-lane march on the x-row bricks for every view
@@ -3144,6 +3241,7 @@ int vr_set_transfer_function(const float *rgba, int n) {
     std::memcpy(g.tf, t, sizeof g.tf);
     g.tf_n = n;
     g.tf_dirty = true;  // uploaded by the next frame that uses it
+    g.tf2_nu = g.tf2_nv = 0;  // at most one of the two tables is set (section 23)
     g.volume_epoch++;
     return VR_OK;
 }
@@ -3151,6 +3249,59 @@ int vr_set_transfer_function(const float *rgba, int n) {
 int vr_transfer_function(float *rgba, int *n) {
     if (rgba && g.tf_n) std::memcpy(rgba, g.tf, (size_t)g.tf_n * 4 * sizeof(float));
     if (n) *n = g.tf_n;
+    return VR_OK;
+}
+
+// ---------------- 2-D transfer function ----------
+
+static_assert(VR_TF2_MAX == vr::kTf2Max, "vr.h repeats vr_internal.h's table size");
+
+int vr_set_transfer_function_2d(const float *rgba, int nu, int nv, int method_v, float v_offset,
+                                float v_scale) {
+    if (!rgba) {  // clear (the other arguments are not read); the 1-D table stays
+        g.tf2_nu = g.tf2_nv = 0;
+        g.volume_epoch++;  // a tile order learned under the table is not reused
+        return VR_OK;
+    }
+    if (nu < 1 || nv < 1 || nu > 256 || nv > 256 || nu * nv > VR_TF2_MAX)
+        return fail(VR_ERR_ARG, "a 2-D transfer function of %d x %d entries (1 .. 256 each, %d in "
+                    "all)", nu, nv, VR_TF2_MAX);
+    const bool mv_ok = (method_v >= 1 && method_v <= 6) ||
+                       (method_v >= VR_QUERY_WEIGHTED && method_v <= VR_QUERY_CROSSING);
+    if (!mv_ok)
+        return fail(VR_ERR_ARG, "method_v %d has no baked plane (1-6, 10-13)", method_v);
+    if (!std::isfinite(v_offset) || !std::isfinite(v_scale))
+        return fail(VR_ERR_ARG, "v_offset / v_scale is not finite");
+    const int n = nu * nv;
+    for (int i = 0; i < 4 * n; i++)
+        if (!std::isfinite(rgba[i]))
+            return fail(VR_ERR_ARG, "transfer function entry (%d, %d), channel %d is not finite",
+                        (i / 4) % nu, (i / 4) / nu, i % 4);
+    float t[4 * VR_TF2_MAX] = {0};  // (rgba may be g.tf2 itself)
+    std::memcpy(t, rgba, (size_t)n * 4 * sizeof(float));
+    std::memcpy(g.tf2, t, sizeof g.tf2);
+    g.tf2_nu = nu;
+    g.tf2_nv = nv;
+    g.tf2_mv = method_v;
+    g.tf2_voff = v_offset;
+    g.tf2_vscale = v_scale;
+    g.tf2_dirty = true;  // uploaded by the next frame that uses it
+    g.tf_n = 0;          // at most one of the two tables is set
+    g.volume_epoch++;
+    return VR_OK;
+}
+
+int vr_transfer_function_2d(float *rgba, int *nu, int *nv, int *method_v, float *v_offset,
+                            float *v_scale) {
+    const bool set = g.tf2_nu != 0;
+    if (rgba && set) std::memcpy(rgba, g.tf2, (size_t)g.tf2_nu * g.tf2_nv * 4 * sizeof(float));
+    if (nu) *nu = g.tf2_nu;
+    if (nv) *nv = g.tf2_nv;
+    if (set) {
+        if (method_v) *method_v = g.tf2_mv;
+        if (v_offset) *v_offset = g.tf2_voff;
+        if (v_scale) *v_scale = g.tf2_vscale;
+    }
     return VR_OK;
 }
 

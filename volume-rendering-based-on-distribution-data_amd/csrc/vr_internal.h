@@ -255,6 +255,20 @@ constexpr int kTfMax = 256;
 // 32-bit plane indices where they fit and VR_TF_WIDE is unset, 64-bit ones otherwise.
 hipError_t launch_march_plane_tf(const float *plane, const Params &P, const float4 *table, int n,
                                  bool cross, uint32_t nslots, hipStream_t s);
+// ---- 2-D transfer function over two planes (vr_transfer2.hip) ----
+// entries of a 2-D table (VR_TF2_MAX of include/vr.h): 16 KiB of LDS as float4; the
+// device copy always holds this many
+constexpr int kTf2Max = 1024;
+// k_march_tf2: k_march_plane_tf's march over two planes pu / pv of one volume (the
+// same dims and pitches P.sy / P.sz, P.nb = 1; pu == pv allowed), one footprint per
+// step for both, classified through the nu x nv (u fastest, nu * nv <= kTf2Max)
+// RGBA entries of the device table at ((su - P.toff) * P.tscale, (sv - voff) *
+// vscale).  cu / cv: that axis' sample is the crossing combine of its 8 corners,
+// else their trilinear blend (vr_last_kernel's M = cu + 2 cv).  Index widths as
+// launch_march_plane_tf.
+hipError_t launch_march_tf2(const float *pu, const float *pv, const Params &P, const float4 *table,
+                            int nu, int nv, float voff, float vscale, bool cu, bool cv,
+                            uint32_t nslots, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
