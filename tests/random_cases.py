@@ -1,5 +1,6 @@
 """Pure case generators of the seeded random sweeps (tests/test_gpu_random.py,
-tests/test_gpu_random_queries.py and the CPU census tests/test_random_cases.py).
+tests/test_gpu_random_queries.py, tests/test_gpu_random_transfer.py and the CPU
+census tests/test_random_cases.py).
 
 No GPU and no library: numpy only.  Every generator maps a seed to a plain dict of
 Python values -- dims, bins or K, dtype, method and query state, W and H, the
@@ -24,6 +25,14 @@ range of the statistic, a maps to 0.08-0.25 of the window and b - a covers
 0.35-0.85 of it, so both ends of the range are coloured in most frames and b runs
 off the window's end in some.  One case in eight keeps a blind window (offset in
 [-0.2, 0.2], scale in [0.5, 2]).
+
+The table sweeps (tf_case, tf2_case, tf_tile_case: frames from baked planes under a
+user-defined 1-D or 2-D table) draw each axis' window by the same rule
+(draw_window); a user table has no transparent ends, so nearly every frame that
+hits the volume is nonzero.  What they deal, so that it is guaranteed: the volume's
+family, the methods of the axes, the table's shape and the kind of its entries, an
+edge shape for one volume in four, a negated window for one case in eight, the
+knobs.
 """
 import math
 
@@ -67,10 +76,9 @@ def _f32(x):
     return float(np.float32(x))
 
 
-def draw_params(rng, stat):
-    """density, brightness and the transfer window for the statistic `stat`"""
-    density = _f32(math.exp(rng.uniform(math.log(0.005), math.log(0.5))))
-    brightness = _f32(rng.uniform(0.5, 2.0))
+def draw_window(rng, stat):
+    """(offset, scale) of a transfer window for the statistic `stat`: the module
+    docstring's rule, one in eight blind"""
     blind = bool(rng.integers(0, 8) == 0)
     u, v = rng.uniform(), rng.uniform()
     if blind:
@@ -79,7 +87,15 @@ def draw_params(rng, stat):
         a, b = SPAN[stat]
         tscale = (0.35 + 0.5 * v) / (b - a)
         toff = a - (0.08 + 0.17 * u) / tscale
-    return dict(density=density, brightness=brightness, toff=_f32(toff), tscale=_f32(tscale))
+    return _f32(toff), _f32(tscale)
+
+
+def draw_params(rng, stat):
+    """density, brightness and the transfer window for the statistic `stat`"""
+    density = _f32(math.exp(rng.uniform(math.log(0.005), math.log(0.5))))
+    brightness = _f32(rng.uniform(0.5, 2.0))
+    toff, tscale = draw_window(rng, stat)
+    return dict(density=density, brightness=brightness, toff=toff, tscale=tscale)
 
 
 def _knobs(rng):
@@ -267,5 +283,187 @@ def gmm_chain_case(seed, direction):
                 translation=tr, redraws=redraws, params=draw_params(rng, stat), knobs=_knobs(rng))
 
 
+# ---- frames from baked planes under a user-defined table (tests/test_gpu_random_transfer.py) ----
+
+# twelve seeds deal 7 record, 2 codec and 3 GMM volumes
+FAMILIES = ("records", "codec", "records", "gmm", "records", "records", "codec", "records",
+            "gmm", "records", "gmm", "records")
+TF_METHODS = {"records": (1, 2, 3, 10, 11, 12, 13), "codec": (4, 5, 6), "gmm": (1, 2, 10, 11, 13)}
+EDGE_NX = (2, 15, 16, 17, 31, 32)   # around the 15-voxel pitch of the planes' 16-wide bricks
+EDGE_NY = (2, 3, 5)                 # one brick of two rows, and odd row counts
+TF_SIZES = (1, 2, 3, 9, 17, 255, 256)
+# (nv, nu): one entry, one row, one column, 1024 entries both ways (many rows: nv = 256),
+# the square, the smallest with both axes, odd sides, and 1020 entries (three whole
+# staging rounds of 256 threads and a partial fourth)
+TF2_SHAPES = ((1, 1), (1, 256), (256, 1), (4, 256), (256, 4), (32, 32), (2, 2), (3, 7), (5, 204))
+TABLE_KINDS = ("unit", "8bit", "wide")
+TF_KNOBS = KNOBS + ({"VR_TF_WIDE": "1"},)
+_RAW_STATS = {1: "mean", 2: "variance", 3: "entropy", 4: "mean", 5: "variance", 6: "entropy"}
+
+
+def _turn(seed):
+    """(family, how many smaller seeds have that family)"""
+    family = FAMILIES[seed % 12]
+    return family, sum(FAMILIES[s % 12] == family for s in range(seed))
+
+
+def make_table(table):
+    """the float32 table of a case's `table` entry: (n, 4) or (nv, nu, 4).  unit:
+    uniform in [0, 1); 8bit: k / 255; wide: RGB in [-0.5, 2), alpha in [-0.25, 1.5)
+    (an alpha outside [0, 1] is legal: nothing in the table is clamped)"""
+    rng = np.random.default_rng(table["seed"])
+    shape = tuple(table["shape"]) + (4,)
+    if table["kind"] == "unit":
+        t = rng.random(shape)
+    elif table["kind"] == "8bit":
+        t = rng.integers(0, 256, shape).astype(np.float32) / np.float32(255)
+    else:
+        t = rng.uniform(-0.5, 2.0, shape)
+        t[..., 3] = rng.uniform(-0.25, 1.5, shape[:-1])
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    assert np.isfinite(t).all()
+    return t
+
+
+def _gmm_axis_query(rng, dtype, method, turn):
+    """draw_gmm_query's state of GMM method 10, 11 or 13: its range, quantile or theta"""
+    whats = ["range", "quantile"] + (["mean", "variance"] if dtype == "f16" else []) + ["crossing"]
+    what = {10: "range", 11: "quantile", 13: "crossing"}[method]
+    _, got, query, stat = draw_gmm_query(rng, dtype, whats.index(what) + len(whats) * turn)
+    assert got == method
+    return query, stat
+
+
+def draw_axis_queries(rng, family, methods, nb, dims, dtype, turn):
+    """draw_query (draw_gmm_query for a GMM volume) once per distinct method of a
+    frame's axes: ({method: query state}, {method: the statistic's name in SPAN}).
+    A record pair (10, 13) holds both the range or weights and the isovalue.  On a
+    GMM volume 10 and 13 read one plane, the range plane: with both in a frame the
+    range is 13's (-inf, theta)."""
+    queries, stats = {}, {}
+    for m in dict.fromkeys(methods):
+        if m <= 6:
+            stats[m] = ("gmm " if family == "gmm" else "") + _RAW_STATS[m]
+        elif family == "records":
+            queries[m], stats[m] = draw_query(rng, m, nb, dims)
+        elif m == 10 and 13 in methods:
+            continue
+        else:
+            queries[m], stats[m] = _gmm_axis_query(rng, dtype, m, turn)
+    if family == "gmm" and 10 in methods and 13 in methods:
+        queries[10] = {"lo": -math.inf, "hi": queries[13]["theta"]}
+        stats[10] = "range"
+    return queries, stats
+
+
+def _negated(stat, off, scale):
+    """the window mirrored: the scale negated and the offset moved to the other end
+    of the statistic's span, so SPAN's ends exchange their places in the table"""
+    a, b = SPAN[stat]
+    return _f32(a + b - off), _f32(-scale)
+
+
+def _tf_volume(rng, seed, family, turn, methods):
+    """what a table case shares with its volume: dims (one seed in four is dealt an
+    edge nx and ny), bins or K, dtype, the query state of the methods"""
+    lo_hi = (2, 25) if family == "gmm" else (2, 33)
+    dims = tuple(int(v) for v in rng.integers(*lo_hi, 3))
+    edge = (seed + seed // 12) % 4 == 1
+    if edge:
+        dims = (EDGE_NX[(seed // 4) % 6], EDGE_NY[(seed // 4 + seed // 24) % 3], dims[2])
+    dtype = ("f32", "f16")[turn % 2]
+    c = dict(family=family, dims=dims, edge=edge, dtype=dtype)
+    if family == "gmm":
+        c["K"] = (8, 16, 32)[turn % 3]
+        nb = None
+    else:
+        nb = c["nb"] = INSTANCE_BINS[(turn // 2) % 6]
+        if family == "codec":  # (one dtype: every bin count in six turns)
+            c["dtype"], nb = "f32", INSTANCE_BINS[turn % 6]
+            c["nb"] = nb
+    c["queries"], c["stats"] = draw_axis_queries(rng, family, methods, nb, dims, dtype, turn)
+    return c
+
+
+def _tf_rest(rng, seed, c, u, v, wmax, hmax):
+    """frame, view, windows, table and knobs of a table case; v None: a 1-D table"""
+    c["W"], c["H"] = _frame(rng, wmax, hmax)
+    tiny = seed % 24 == 7   # dealt: a 1 x 1 frame, seen from inside so that its ray hits
+    if tiny:
+        c["W"], c["H"] = 1, 1
+    c["kind"], c["rotation"], c["translation"] = draw_view(rng, 2 if tiny else None)
+    c["params"] = draw_params(rng, c["stats"][u])
+    negate = seed % 8 == 5
+    flip_v = negate and v is not None and (seed // 8) % 2 == 1
+    if v is not None:
+        c["voff"], c["vscale"] = draw_window(rng, c["stats"][v])
+        if flip_v:
+            c["voff"], c["vscale"] = _negated(c["stats"][v], c["voff"], c["vscale"])
+        shape = TF2_SHAPES[(seed + seed // 9) % 9]
+    else:
+        shape = (TF_SIZES[seed % 7],)
+    if negate and not flip_v:
+        p = c["params"]
+        p["toff"], p["tscale"] = _negated(c["stats"][u], p["toff"], p["tscale"])
+    c["negated"] = ("v" if flip_v else "u") if negate else None
+    c["table"] = dict(shape=shape, kind=TABLE_KINDS[(seed + seed // 7) % 3],
+                      seed=int(rng.integers(1, 1 << 20)))
+    c["knobs"] = dict(TF_KNOBS[(seed + seed // 4) % 4])
+    return c
+
+
+def tf_case(seed):
+    """a whole frame from a baked plane under a 1-D table (k_march_plane_tf).  Dealt
+    by the seed: the family (FAMILIES), within it the method (every one in turn), the
+    dtype and the bin count or K; the table's size (TF_SIZES) and kind (TABLE_KINDS);
+    the knobs (TF_KNOBS); one seed in four an edge shape, one in eight a negated
+    window, one in 24 a 1 x 1 frame with the eye inside the volume.  Drawn: the
+    other dims, frame, view, query state, window, table seed."""
+    rng = np.random.default_rng(9500 + seed)
+    family, turn = _turn(seed)
+    u = TF_METHODS[family][turn % len(TF_METHODS[family])]
+    c = dict(sweep="tf", seed=seed, u=u, v=None, **_tf_volume(rng, seed, family, turn, (u,)))
+    return _tf_rest(rng, seed, c, u, None, 96, 72)
+
+
+def _tf2_pair(family, turn):
+    """(u, v) of a 2-D case: the four (CU, CV) instances in turn -- neither axis
+    method 13, only u, only v, both (a codec volume has no method 13) -- the other
+    methods in turn, u == v (one plane, bound twice) every fifth time"""
+    if family == "codec":
+        return 4 + turn % 3, 4 + (turn + turn // 3) % 3
+    rest = tuple(m for m in TF_METHODS[family] if m != 13)
+    inst, j = turn % 4, turn // 4
+    a = rest[j % len(rest)]
+    b = a if j % 5 == 4 else rest[(j + 1 + j // 3) % len(rest)]
+    return ((a, b), (13, a), (a, 13), (13, 13))[inst]
+
+
+def tf2_case(seed):
+    """a whole frame from two baked planes under a 2-D table (k_march_tf2): tf_case's
+    deals with the pair of _tf2_pair, the table's shape (TF2_SHAPES) and v's window
+    by draw_window; every second negated window is v's"""
+    rng = np.random.default_rng(10000 + seed)
+    family, turn = _turn(seed)
+    u, v = _tf2_pair(family, turn)
+    c = dict(sweep="tf2", seed=seed, u=u, v=v, **_tf_volume(rng, seed, family, turn, (u, v)))
+    return _tf_rest(rng, seed, c, u, v, 96, 72)
+
+
+def tf_tile_case(seed):
+    """a frame under a 1-D (even seeds) or a 2-D table split over 2-8 ranks' tile
+    lists; the methods are drawn"""
+    rng = np.random.default_rng(10500 + seed)
+    family, turn = _turn(seed)
+    methods = TF_METHODS[family]
+    u = int(methods[int(rng.integers(0, len(methods)))])
+    v = int(methods[int(rng.integers(0, len(methods)))]) if seed % 2 else None
+    c = dict(sweep="tftiles", seed=seed, u=u, v=v, world=2 + seed % 7,
+             **_tf_volume(rng, seed, family, turn, (u,) if v is None else (u, v)))
+    return _tf_rest(rng, seed, c, u, v, 200, 120)
+
+
 SWEEPS = {"hist": (hist_query_case, 96), "tiles": (hist_tile_case, 24), "f16": (f16_case, 48),
-          "gmm": (gmm_case, 40), "chain": (gmm_chain_case, 16)}
+          "gmm": (gmm_case, 40), "chain": (gmm_chain_case, 16),
+          "tf": (tf_case, 56), "tf2": (tf2_case, 72), "tftiles": (tf_tile_case, 16)}
+TF_SWEEPS = ("tf", "tf2", "tftiles")

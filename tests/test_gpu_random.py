@@ -4,7 +4,9 @@ the volume), image size, method, render parameters, kernel path override and
 statistics source (per-step decode / baked), renders through the C-ABI and
 compares with the oracle.  Same bar as test_gpu_parity.py: packed RGBA8 and
 samples per pixel identical, float RGBA within 1e-4.  Cases are reproducible
-from their seed (printed in the failure message)."""
+from their seed (printed in the failure message).  The query, f16 and GMM marches
+are swept by test_gpu_random_queries.py, the table marches by
+test_gpu_random_transfer.py."""
 import numpy as np
 import pytest
 

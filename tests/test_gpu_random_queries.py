@@ -7,6 +7,9 @@ test_gpu_random.py does for methods 1/2/3/7 on fp32 records, for
   k_march_gmm_h, k_march_gmm_range(_h), k_march_gmm_quant(_h), the GMM planes and
   method 13 on the range plane; slab chains of all of them.
 
+The table marches (k_march_plane_tf, k_march_tf2) have their sweep, from the same
+generators module, in tests/test_gpu_random_transfer.py.
+
 Every case is random_cases' dict of its seed: the camera is row-aligned, an exact
 quarter turn, inside the volume or oblique, the frame is anything from 1 x 1, the
 density runs from rays that cross the volume unsaturated to rays that end within

@@ -1,5 +1,6 @@
 """CPU census of the random query sweeps (tests/random_cases.py, run on the GPU by
-tests/test_gpu_random_queries.py): the generators and the references only.  It keeps
+tests/test_gpu_random_queries.py and tests/test_gpu_random_transfer.py): the
+generators and the references only.  It keeps
 the sweeps from going vacuous -- frames of nothing, or draws that never reach the
 geometry they are there for -- and holds the helpers that turn a case dict into its
 volume, camera and reference frame, which the GPU tests import.
@@ -18,11 +19,37 @@ the eye inside the volume, exact quarter turns; frames with W < 64 or H < 4.
   f16       48       0        5 |      8          33    17 |      9      16     33
   gmm       40       0        0 |      5          29    13 |     11      10     29
   chain     16       0        0 |      2           8     4 |      9       2      8
+  tf        56       0        1 |     10          43    14 |     14      17     35
+  tf2       72       0        1 |     18          55    16 |     18      20     54
+  tftiles   16       0        0 |      3          12     5 |      6       3      5
 
 (opaque is a lower bound: the final opacity can be told from the float frame only
 where alpha * brightness stays below 1.)  A transfer window drawn blindly, as
 test_gpu_random.draw_params draws it, left 35 of 96 method-10 frames without a
 nonzero pixel; random_cases.draw_params places the window on the statistic's range.
+
+The last three sweeps are the table marches' (tests/test_gpu_random_transfer.py:
+frames from baked planes under a user-defined 1-D or 2-D table).  Their references
+are ref_transfer.render_plane and ref_transfer2.render_planes over the planes numpy
+computes per voxel (tf_plane).  For them the census also counts, as printed by
+test_table_frames_reach_what_they_are_for: cases with samples on a footprint the
+volume's edge clamps; nonzero frames of a volume dealt an edge nx (2, 15, 16, 17, 31,
+32) and ny (2, 3, 5); 1 x 1 frames whose ray takes samples; 1-D frames that differ in
+RGBA8 from the same planes and window under the built-in rainbow; `wide` tables
+(entries outside [0, 1]) with a ray whose alpha ends below its alpha under the
+table's abs(), so that opacity fell along it; and, for the 2-D whole frames, how
+many differ in RGBA8 from each argument-level mutant of their reference, out of
+those where the mutant can matter -- row 0 repeated over all rows (nv >= 2), column 0
+over all columns (nu >= 2), v's window replaced by u's (nv >= 2 and the windows
+differ), the two blends exchanged (exactly one axis is method 13), the two planes
+exchanged under the same windows and blends (u != v and the planes differ: a GMM
+volume's 10 and 13 are one plane).  Each must reach half; a sweep whose frames do
+not notice a mutant would not notice that bug in the kernel either.
+
+  sweep    clamped edge-nx 1x1 | rainbow  fell | row 0  column 0  u's window  blends planes
+  tf         51/56      13   3 |   55/55  4/18 |
+  tf2        64/72      18   3 |         12/23 | 53/56     54/56       53/56   27/29  40/46
+  tftiles    14/16       4   1 |           3/6 |
 """
 import functools
 import math
@@ -35,7 +62,10 @@ import ref_crossing
 import ref_distance
 import ref_gmm_quantile
 import ref_gmm_range
+import ref_numpy
 import ref_quantile
+import ref_transfer
+import ref_transfer2
 import ref_weighted
 
 f32 = np.float32
@@ -117,19 +147,34 @@ def hist_reference_by_plane(pkg, case, vol, m):
     ref_weighted.render bit for bit by tests/test_crossing.py).  Used where frames
     are large (tile lists) and by the census; test_plane_route_is_the_reference
     holds the two against each other."""
-    W, H, q, kw = case["W"], case["H"], case["query"], render_kw(case)
+    return ref_crossing.render_plane(record_plane(pkg, case, vol), case["W"], case["H"], m,
+                                     blend=blend_of(case["method"]), **render_kw(case))
+
+
+def blend_of(method):
+    """what makes a sample of a plane's 8 corners: the crossing combine for method
+    13's plane of F, the trilinear blend for every other"""
+    return ref_crossing.combine if method == 13 else ref_crossing.trilinear
+
+
+def record_plane(pkg, case, vol):
+    """the plane of case["method"] on the records vol as numpy computes it, (nz, ny,
+    nx) float32: what bake_stats (1/2/3), bake_weighted, bake_quantile, bake_distance
+    and bake_crossing hold per voxel.  A float16 vol is widened first."""
+    method, q = case["method"], case["query"]
     wide = np.asarray(vol).astype(np.float32)
-    blend = ref_crossing.trilinear
-    if case["method"] == 10:
-        plane = ref_weighted.lin_stat(wide, query_weights(pkg, case))
-    elif case["method"] == 11:
-        plane = ref_quantile.quantile_stat(wide, quantile_arg(q))
-    elif case["method"] == 12:
-        plane = ref_distance.distance_stat(wide, distance_target(case, vol), q["metric"],
-                                           q["similarity"])
-    else:
-        plane, blend = ref_crossing.cdf_plane(vol, query_weights(pkg, case)), ref_crossing.combine
-    return ref_crossing.render_plane(plane, W, H, m, blend=blend, **kw)
+    with np.errstate(all="ignore"):
+        if method in (1, 2, 3):
+            return ref_numpy.stat(wide, method - 1)
+        if method == 10:
+            return ref_weighted.lin_stat(wide, query_weights(pkg, case))
+        if method == 11:
+            return ref_quantile.quantile_stat(wide, quantile_arg(q))
+        if method == 12:
+            return ref_distance.distance_stat(wide, distance_target(case, vol), q["metric"],
+                                              q["similarity"])
+    assert method == 13
+    return ref_crossing.cdf_plane(vol, query_weights(pkg, case))
 
 
 def gmm_records(orc, case, z_base=0, nslices=None):
@@ -172,6 +217,86 @@ def f16_reference(orc, case, vol, m):
     return orc.render(wide, oracle_params(orc, case, m, m7_dims=case["m7"]))[:3]
 
 
+# ---- frames from baked planes under a table (random_cases.tf_case and the like) ----
+
+def axis_case(case, method):
+    """a table case as the helpers of one method read it: `method` and its `query`"""
+    return dict(case, method=method, query=case["queries"].get(method, {}))
+
+
+def tf_methods(case):
+    return (case["u"],) if case["v"] is None else (case["u"], case["v"])
+
+
+def tf_records(orc, case):
+    """the family's records: hist_volume's, synth_codec's triple or gmm_records' pair"""
+    if case["family"] == "records":
+        return hist_volume(orc, case)
+    if case["family"] == "codec":
+        return orc.synth_codec(*case["dims"], case["nb"], seed=case["seed"])
+    return gmm_records(orc, case)
+
+
+def gmm_oracle_plane(orc, wide, method):
+    """the oracle's mean (method 1) or variance statistic (2) of every voxel.  The
+    census only: the library's planes meet these within 1e-4, not bit for bit."""
+    wm, sg = wide
+    flat_wm, flat_sg = wm.reshape(-1, *wm.shape[-2:]), sg.reshape(-1, sg.shape[-1])
+    out = np.array([orc.gmm_stat(a, b, method) for a, b in zip(flat_wm, flat_sg)], np.float32)
+    return out.reshape(sg.shape[:-1])
+
+
+def tf_plane(pkg, orc, case, method, records):
+    """the baked plane of `method` of a table case as numpy computes it, (nz, ny, nx)
+    float32: record_plane for record volumes, ref_numpy's codec statistics of the
+    decoded records, ref_gmm_range and ref_gmm_quantile per voxel for a GMM volume's
+    queries (10 and 13 are both the range plane), the oracle for its mean and
+    variance"""
+    if case["family"] == "records":
+        return record_plane(pkg, axis_case(case, method), records)
+    with np.errstate(all="ignore"):
+        if case["family"] == "codec":
+            return ref_numpy.codec_stat(ref_numpy.codec_decode(*records), method - 4)
+        wm, sg = records[1]
+        table, steps = gmm_consts(pkg)
+        q = case["queries"].get(method)
+        if method == 10:
+            return ref_gmm_range.range_stat(wm, sg, q["lo"], q["hi"], table)
+        if method == 13:
+            return ref_gmm_range.range_stat(wm, sg, -math.inf, q["theta"], table)
+        if method == 11:
+            spread = q["state"] == "spread"
+            lo, hi = (q["lo"], q["hi"]) if spread else (q["q"], q["q"])
+            return ref_gmm_quantile.quantile_stat(wm, sg, lo, hi, spread, table, steps)
+    return gmm_oracle_plane(orc, records[1], method)
+
+
+def tf_planes(pkg, orc, case, records=None):
+    """{method: plane} of the case's axes"""
+    records = tf_records(orc, case) if records is None else records
+    return {mth: tf_plane(pkg, orc, case, mth, records) for mth in dict.fromkeys(tf_methods(case))}
+
+
+def tf_reference(case, planes, m, table=None, info=None, swap_blends=False, swap_planes=False,
+                 v_window=None, rainbow=False):
+    """(RGBA8, float RGBA, samples) of a table case over `planes`: ref_transfer's frame
+    for a 1-D table, ref_transfer2's for a 2-D one.  The other arguments are the
+    census's mutants: another table, the blends or the planes of the two axes
+    exchanged, another window for v, the built-in rainbow for a 1-D table."""
+    W, H, u, v, kw = case["W"], case["H"], case["u"], case["v"], render_kw(case)
+    table = rc.make_table(case["table"]) if table is None else table
+    if v is None:
+        if rainbow:
+            return ref_crossing.render_plane(planes[u], W, H, m, blend=blend_of(u), info=info, **kw)
+        return ref_transfer.render_plane(planes[u], W, H, m, table, blend=blend_of(u), info=info,
+                                         **kw)
+    pu, pv = (planes[v], planes[u]) if swap_planes else (planes[u], planes[v])
+    bu, bv = (blend_of(v), blend_of(u)) if swap_blends else (blend_of(u), blend_of(v))
+    voff, vscale = (case["voff"], case["vscale"]) if v_window is None else v_window
+    return ref_transfer2.render_planes(pu, pv, W, H, m, table, blend_u=bu, blend_v=bv, voff=voff,
+                                       vscale=vscale, info=info, **kw)
+
+
 # ---- the census ----
 
 def eye_inside(m):
@@ -193,8 +318,55 @@ def frame_census(case, m, rgba8, rgba_f, n):
                 narrow=case["W"] < 64 or case["H"] < 4)
 
 
-def reference_frame(pkg, orc, case):
+def table_census(case, m, planes, ref, info):
+    """what a table case's reference adds to frame_census: samples on a clamped
+    footprint; for a whole frame with a nonzero pixel whether it differs in RGBA8
+    from the frame under the built-in rainbow (1-D) and from each argument-level
+    mutant of ref_transfer2.render_planes that can matter for the case (None where
+    it cannot), and for a `wide` table whether some ray's alpha ends below its alpha
+    under the table's abs(): opacity fell along it"""
+    u, v, nonzero = case["u"], case["v"], bool(np.any(ref[0] != 0))
+    row = dict(clamped=info["clamped"] > 0, edge_nonzero=case["edge"] and nonzero, rainbow=None,
+               tiny_hit=ref[2].shape == (1, 1) and bool(ref[2][0, 0] > 0),
+               fell=None, mutants={k: None for k in MUTANTS})
+    if not nonzero:
+        return row
+    table = rc.make_table(case["table"])
+    differs = lambda **kw: bool(np.any(tf_reference(case, planes, m, **kw)[0] != ref[0]))
+    if case["table"]["kind"] == "wide":
+        plain = tf_reference(case, planes, m, table=np.abs(table))
+        row["fell"] = bool(np.any((ref[2] >= 0) & (ref[1][..., 3] < plain[1][..., 3])))
+    if case["sweep"] == "tftiles":  # (the larger frames: the whole-frame sweeps hold the rest)
+        return row
+    if v is None:
+        row["rainbow"] = differs(rainbow=True)
+        return row
+    nv, nu = table.shape[:2]
+    window = (case["params"]["toff"], case["params"]["tscale"])
+    can = {"row 0": nv >= 2, "column 0": nu >= 2,
+           "u's window": nv >= 2 and window != (case["voff"], case["vscale"]),
+           "blends": (u == 13) != (v == 13),
+           "planes": u != v and not np.array_equal(planes[u], planes[v], equal_nan=True)}
+    args = {"row 0": dict(table=np.repeat(table[:1], nv, axis=0)),
+            "column 0": dict(table=np.repeat(table[:, :1], nu, axis=1)),
+            "u's window": dict(v_window=window), "blends": dict(swap_blends=True),
+            "planes": dict(swap_planes=True)}
+    for k in MUTANTS:
+        if can[k]:
+            row["mutants"][k] = differs(**args[k])
+    return row
+
+
+def reference_frame(pkg, orc, case, extra=None):
+    """(camera, (RGBA8, float RGBA, samples)) of a case; extra: a dict that receives a
+    table case's table_census"""
     m = camera(pkg, case)
+    if case["sweep"] in rc.TF_SWEEPS:
+        planes, info = tf_planes(pkg, orc, case), {}
+        ref = tf_reference(case, planes, m, info=info)
+        if extra is not None:
+            extra.update(table_census(case, m, planes, ref, info))
+        return m, ref
     if case["sweep"] in ("hist", "tiles"):
         return m, hist_reference_by_plane(pkg, case, hist_volume(orc, case), m)
     if case["sweep"] == "f16":
@@ -206,18 +378,23 @@ def reference_frame(pkg, orc, case):
 TYPES = ("opaque", "unsaturated", "short", "inside", "quarter", "narrow")
 # the seeds whose reference frames the census renders (all of them where that is quick)
 CENSUS_SEEDS = {"hist": range(96), "tiles": range(24), "f16": range(48), "gmm": range(40),
-                "chain": range(16)}
+                "chain": range(16), "tf": range(56), "tf2": range(72), "tftiles": range(16)}
+# the argument-level mutants of a 2-D frame's reference (table_census)
+MUTANTS = ("row 0", "column 0", "u's window", "blends", "planes")
 
 
+@functools.lru_cache(maxsize=None)
 def census(pkg, orc, sweep):
+    """one row per seed (computed once per sweep: two tests read the table sweeps')"""
     rows = []
     for seed in CENSUS_SEEDS[sweep]:
         case = make_case(pkg, sweep, seed)
         if not case.get("supported", True):
             rows.append(None)  # the library refuses the query: no frame
             continue
-        m, ref = reference_frame(pkg, orc, case)
-        rows.append(frame_census(case, m, *ref))
+        extra = {}
+        m, ref = reference_frame(pkg, orc, case, extra)
+        rows.append(dict(frame_census(case, m, *ref), case=case, **extra))
     return rows
 
 
@@ -239,12 +416,98 @@ def test_reference_frames_are_worth_comparing(pkg, orc, sweep):
         assert counts["inside"] >= 4
 
 
+@pytest.mark.parametrize("sweep", rc.TF_SWEEPS)
+def test_table_frames_reach_what_they_are_for(pkg, orc, sweep):
+    """the table sweeps, by the reference alone: at least one case in four takes
+    samples on a clamped footprint and at least four nonzero frames come from an edge
+    nx; three 1-D frames in four differ from the frame under the built-in rainbow;
+    every mutant of a 2-D frame's reference changes at least half of the frames where
+    it can; opacity falls along a ray of at least two `wide` frames; the ray of at
+    least two 1 x 1 frames (one of the tile sweep's) takes samples"""
+    rows = census(pkg, orc, sweep)
+    share = lambda flags: (sum(flags), len(flags))
+    clamped = sum(r["clamped"] for r in rows)
+    edge = sum(r["edge_nonzero"] for r in rows)
+    rainbow = share([r["rainbow"] for r in rows if r["rainbow"] is not None])
+    fell = share([r["fell"] for r in rows if r["fell"] is not None])
+    mutants = {k: share([r["mutants"][k] for r in rows if r["mutants"][k] is not None])
+               for k in MUTANTS}
+    tiny = sum(r["tiny_hit"] for r in rows)
+    print(f"{sweep}: clamped {clamped}, edge nx nonzero {edge}, 1 x 1 hit {tiny}, differ from "
+          f"the rainbow {rainbow[0]}/{rainbow[1]}, opacity fell {fell[0]}/{fell[1]}, mutants "
+          + ", ".join(f"{k} {a}/{b}" for k, (a, b) in mutants.items()))
+    assert 4 * clamped >= len(rows), (sweep, clamped)
+    assert edge >= 4, (sweep, edge)
+    assert tiny >= (1 if sweep == "tftiles" else 2), (sweep, tiny)
+    if sweep == "tf":
+        assert rainbow[1] >= 28 and 4 * rainbow[0] >= 3 * rainbow[1], rainbow
+    if sweep == "tf2":
+        for k, (a, b) in mutants.items():
+            assert b >= 8 and 2 * a >= b, (k, a, b)
+    assert fell[0] >= 2, fell
+
+
 def _count(cases, **want):
     return sum(all(c.get(k) == v for k, v in want.items()) for c in cases)
 
 
 def _count_query(cases, **want):
     return sum(all(c["query"].get(k) == v for k, v in want.items()) for c in cases)
+
+
+def _table_sweeps_deal_their_combinations(cases):
+    """what random_cases deals to the table sweeps, guaranteed and not merely likely"""
+    tf, tf2, tiles = cases["tf"], cases["tf2"], cases["tftiles"]
+    for sweep in (tf, tf2, tiles):
+        n = len(sweep)
+        assert 2 * _count(sweep, family="records") > n
+        assert 6 * _count(sweep, family="codec") >= n and 6 * _count(sweep, family="gmm") >= n
+        for knobs in rc.TF_KNOBS:  # both index widths: VR_TF_WIDE set and not
+            assert _count(sweep, knobs=knobs) >= 4, knobs
+        assert _count(sweep, edge=True) * 4 >= n - 3
+        assert _count(sweep, W=1, H=1, kind=2) >= (2 if n > 24 else 1)
+        assert {c["dims"][0] for c in sweep if c["edge"]} <= set(rc.EDGE_NX)
+        assert {c["dims"][1] for c in sweep if c["edge"]} <= set(rc.EDGE_NY)
+        for kind in rc.TABLE_KINDS:
+            assert sum(c["table"]["kind"] == kind for c in sweep) >= 2, kind
+        for c in sweep:
+            t = rc.make_table(c["table"])
+            assert t.dtype == np.float32 and np.isfinite(t).all() and t.size <= 4 * 1024
+            assert t.shape == tuple(c["table"]["shape"]) + (4,)
+            assert set(c["stats"]) == set(tf_methods(c)) and set(c["queries"]) <= set(c["stats"])
+            assert all(mth in rc.TF_METHODS[c["family"]] for mth in tf_methods(c)), c
+            if c["family"] == "records":  # a pair (10, 13) holds both states
+                assert set(c["queries"]) == {mth for mth in tf_methods(c) if mth >= 10}, c
+    for sweep in (tf, tf2):
+        assert {c["dims"][0] for c in sweep if c["edge"]} == set(rc.EDGE_NX)
+        assert {c["dims"][1] for c in sweep if c["edge"]} == set(rc.EDGE_NY)
+        assert all(_count(sweep, family=f, edge=True) >= 1 for f in rc.TF_METHODS)
+        assert _count(sweep, negated="u") >= 2
+        for dtype in ("f32", "f16"):
+            assert _count(sweep, family="records", dtype=dtype) >= 2
+            assert _count(sweep, family="gmm", dtype=dtype) >= 2
+        for nb in rc.INSTANCE_BINS:
+            assert _count(sweep, family="records", nb=nb) >= 2, nb
+            assert _count(sweep, family="codec", nb=nb) >= 1, nb
+        for K in (8, 16, 32):
+            assert _count(sweep, K=K) >= 2, K
+    for family, methods in rc.TF_METHODS.items():
+        for u in methods:
+            assert _count(tf, family=family, u=u) >= 2, (family, u)
+    for n in rc.TF_SIZES:
+        assert sum(c["table"]["shape"] == (n,) for c in tf) >= 2, n
+    assert all(c["v"] is None for c in tf) and all(c["v"] is not None for c in tf2)
+    for cu in (False, True):
+        for cv in (False, True):
+            assert sum((c["u"] == 13) == cu and (c["v"] == 13) == cv for c in tf2) >= 4, (cu, cv)
+    assert sum(c["u"] == c["v"] for c in tf2) >= 2
+    assert sum(c["u"] == c["v"] != 13 for c in tf2) >= 2   # one blended plane bound twice
+    assert any(set(tf_methods(c)) == {10, 13} and c["family"] == "records" for c in tf2)
+    for shape in rc.TF2_SHAPES:
+        assert sum(c["table"]["shape"] == shape for c in tf2) >= 2, shape
+    assert _count(tf2, negated="v") >= 2
+    assert {c["world"] for c in tiles} >= set(range(2, 9))
+    assert _count(tiles, v=None) == len(tiles) // 2
 
 
 def test_every_combination_occurs_twice(pkg):
@@ -271,6 +534,7 @@ def test_every_combination_occurs_twice(pkg):
     for knobs in rc.KNOBS:
         for s in cases:
             assert _count(cases[s], knobs=knobs) >= 2, (s, knobs)
+    _table_sweeps_deal_their_combinations(cases)
     tiles = cases["tiles"]
     for method in (10, 11, 12, 13):
         assert _count(tiles, method=method) >= 2, method
@@ -320,12 +584,19 @@ def test_cases_are_reproducible_and_in_bounds(pkg):
         for seed in range(n):
             c = make_case(pkg, sweep, seed)
             assert c == make_case(pkg, sweep, seed)
-            assert 1 <= c["W"] <= (200 if sweep == "tiles" else 96)
-            assert 1 <= c["H"] <= (120 if sweep == "tiles" else 72)
-            assert max(c["dims"]) <= (24 if "K" in c else 32) and min(c["dims"]) >= 2
+            assert 1 <= c["W"] <= (200 if sweep in ("tiles", "tftiles") else 96)
+            assert 1 <= c["H"] <= (120 if sweep in ("tiles", "tftiles") else 72)
+            # (a GMM volume of a table sweep may be dealt an edge nx of 31 or 32)
+            assert max(c["dims"][1:]) <= (24 if "K" in c else 32) and min(c["dims"]) >= 2
+            assert c["dims"][0] <= (24 if "K" in c and not c.get("edge") else 32)
             assert 0.005 <= c["params"]["density"] <= 0.5001
             if sweep == "chain":
                 assert c["dims"][2] >= c["nslabs"]
+            if sweep in rc.TF_SWEEPS:
+                assert c == eval(repr(c), {"inf": math.inf})  # printable: a failure shows it whole
+                for off, scale in ((c["params"]["toff"], c["params"]["tscale"]),
+                                   (c.get("voff", 0.0), c.get("vscale", 1.0))):
+                    assert math.isfinite(off) and math.isfinite(scale) and scale != 0
 
 
 @pytest.mark.parametrize("seed", (0, 1, 2, 3))
