@@ -1113,6 +1113,47 @@ int vr_set_transfer_function_2d(const float *rgba, int nu, int nv, int method_v,
 int vr_transfer_function_2d(float *rgba, int *nu, int *nv, int *method_v, float *v_offset,
                             float *v_scale);
 
+/* ---- ray projections of baked planes ----
+ * What is done with the samples along a ray.  VR_PROJ_COMPOSITE (the default) is
+ * the front-to-back emission-absorption integral with early termination, every
+ * path exactly as without this state.  Under the other three a ray is set up and
+ * stepped as ever (sample i at pos, t += 0.01, the ray ends when t > tfar or after
+ * 500 samples) but no opacity test is made, and its n samples are reduced in
+ * float32, in step order:
+ *     VR_PROJ_MAX   acc = -inf; acc = (s > acc) ? s : acc   (a NaN sample is skipped)
+ *     VR_PROJ_MIN   acc = +inf; acc = (s < acc) ? s : acc
+ *     VR_PROJ_MEAN  sum = 0; sum = sum + s; acc = sum / (float)n
+ * The ray's one value is then classified as a sample is, x = (acc -
+ * transfer_offset) * transfer_scale through the table of vr_set_transfer_function
+ * if one is set, else the built-in nine entries, and the pixel is (r a, g a, b a,
+ * a) times brightness, clamped and packed as ever; d_steps receives n.  density is
+ * not read: it is the opacity of one step, and a projection has no steps to weigh.
+ *
+ * vr_set_projection: one of the four modes; anything else is VR_ERR_ARG and the
+ * state stays as it was.  Host state only: no device call, so it may be set before
+ * a volume is resident.  Like the table it is the caller's: it survives new volumes,
+ * vr_convert_f16, every vr_release_* and freeCudaBuffers; only
+ * vr_set_projection(VR_PROJ_COMPOSITE) clears it.  Changing it starts the adaptive
+ * tile order afresh.  vr_projection: the mode.
+ *
+ * With a projection set, vr_render / render_kernel and vr_render_gmm_baked serve
+ * exactly the frames a 1-D table serves -- the resident baked plane of methods
+ * 1/2/3, 4/5/6 and 10-13 (13: the crossing combine of the 8 corners), of GMM
+ * methods 1, 2, 10, 11 and 13 -- marched in the plane's own bricks for every view
+ * (k_march_proj; vr_last_kernel: k_march_proj_max / _min / _mean<B=1,M=0 or 13>);
+ * tile lists, d_output_f, d_steps, clipped coverage, VR_TF_WIDE and VR_WG_PER_CU as
+ * under the table.  Everything else -- a plane that is not baked, methods 7 and
+ * 8/9/0, vr_render_gmm and slab chains, vr_count_footprint, vr_footprint_bytes,
+ * vr_gmm_count_footprint(_slab), and any frame while a 2-D table is set (a
+ * projection classifies one plane) -- is VR_ERR_UNSUPPORTED: bake first, or clear
+ * the projection.  Nothing falls back to compositing. */
+#define VR_PROJ_COMPOSITE 0
+#define VR_PROJ_MAX 1
+#define VR_PROJ_MIN 2
+#define VR_PROJ_MEAN 3
+int vr_set_projection(int mode);
+int vr_projection(void);
+
 /* library version string */
 const char *vr_version(void);
 

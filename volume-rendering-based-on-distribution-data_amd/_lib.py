@@ -28,6 +28,7 @@ VR_DIST_EMD = 1
 VR_DIST_KS = 2
 VR_QUERY_CROSSING = 13
 VR_TF_MAX = 256  # entries of a user-defined transfer function
+VR_PROJ_MAX, VR_PROJ_MIN, VR_PROJ_MEAN = 1, 2, 3  # ray projections (0: composite)
 VR_TF2_MAX = 1024  # entries (nu * nv) of a 2-D one
 
 
@@ -127,6 +128,7 @@ EXPORTS = [
     "vr_release_crossing", "vr_crossing_info",
     "vr_set_transfer_function", "vr_transfer_function",
     "vr_set_transfer_function_2d", "vr_transfer_function_2d",
+    "vr_set_projection", "vr_projection",
 ]
 
 _lib = None
@@ -345,6 +347,10 @@ def load() -> ctypes.CDLL:
     L.vr_set_transfer_function_2d.restype = i32
     L.vr_transfer_function_2d.argtypes = [vp] * 6
     L.vr_transfer_function_2d.restype = i32
+    L.vr_set_projection.argtypes = [i32]
+    L.vr_set_projection.restype = i32
+    L.vr_projection.argtypes = []
+    L.vr_projection.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

@@ -1035,6 +1035,34 @@ def transfer_function_2d():
             off.value, scale.value)
 
 
+# ------------------- ray projections of baked planes
+
+PROJ_MAX, PROJ_MIN, PROJ_MEAN = _lib.VR_PROJ_MAX, _lib.VR_PROJ_MIN, _lib.VR_PROJ_MEAN
+_PROJ_NAMES = {None: 0, "max": PROJ_MAX, "min": PROJ_MIN, "mean": PROJ_MEAN}
+
+
+def set_projection(mode) -> None:
+    """What is done with the samples along a ray: "max", "min" or "mean" (or PROJ_MAX
+    / PROJ_MIN / PROJ_MEAN) reduces every ray's samples to that one value -- no opacity
+    test, no early end -- and classifies it once, through the table of
+    set_transfer_function if one is set, else the built-in one; None (or 0) returns to
+    compositing.  Host state only, the caller's like the table: it survives new
+    volumes and freeCudaBuffers.  While a projection is set frames come from baked
+    planes, as under a 1-D table; everything else, and any frame while a 2-D table is
+    set, raises VRError (VR_ERR_UNSUPPORTED)."""
+    if mode is None or isinstance(mode, str):
+        if mode not in _PROJ_NAMES:
+            raise ValueError(f'a projection is "max", "min", "mean" or None, got {mode!r}')
+        mode = _PROJ_NAMES[mode]
+    check(_lib.load().vr_set_projection(int(mode)))
+
+
+def projection():
+    """The projection set: "max", "min" or "mean"; None: frames are composited."""
+    m = _lib.load().vr_projection()
+    return {v: k for k, v in _PROJ_NAMES.items()}[m]
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -1063,5 +1091,6 @@ __all__ = [
     "gmm_quantile_steps", "bake_gmm_quantile", "release_gmm_quantile", "gmm_quantile_info",
     "TF_MAX", "REFERENCE_TF", "set_transfer_function", "transfer_function",
     "TF2_MAX", "set_transfer_function_2d", "transfer_function_2d",
+    "PROJ_MAX", "PROJ_MIN", "PROJ_MEAN", "set_projection", "projection",
     "VRError", "PAD",
 ]

@@ -147,6 +147,15 @@ struct State {
     float4 *tf2_dev = nullptr;
     bool tf2_dirty = false;
     hipStream_t tf2_stream = nullptr;
+    // ray projection: VR_PROJ_COMPOSITE (0: every path as
+    // without it), VR_PROJ_MAX, _MIN or _MEAN.  The caller's, like the tables: tied to
+    // no volume.  Host state; rtf_dev is the device copy of the built-in nine entries
+    // (kTfMax float4, nullptr: not made) that a projection without a caller's table
+    // classifies through, made by the frame that needs it (rtf_upload).
+    int proj = 0;
+    float4 *rtf_dev = nullptr;
+    bool rtf_dirty = false;
+    hipStream_t rtf_stream = nullptr;
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -1863,6 +1872,9 @@ void release_tf_device() {
     if (g.tf2_dev) (void)hipFree(g.tf2_dev);
     g.tf2_dev = nullptr;
     g.tf2_dirty = false;
+    if (g.rtf_dev) (void)hipFree(g.rtf_dev);
+    g.rtf_dev = nullptr;
+    g.rtf_dirty = false;
 }
 
 // A frame of P's grid from `plane` (one float per voxel in x-row bricks of pitches
@@ -1953,6 +1965,59 @@ int render_tf2_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots,
     return launch_tf2_frame(P, nslots, u.ptr(), v.ptr(), u.pl->sy, u.pl->sz, u.cross, v.cross);
 }
 
+// ---- ray projections of baked planes ----
+
+// What has no plane march under a projection is refused, never composited.
+int proj_refuse(const char *what) {
+    static const char *const kName[] = {"", "maximum", "minimum", "mean"};
+    if (g.tf2_nu)
+        return fail(VR_ERR_UNSUPPORTED, "%s: the %s projection classifies one plane, and a 2-D "
+                                        "transfer function is set (clear the table with "
+                                        "vr_set_transfer_function_2d(NULL, 0, 0, 0, 0, 0), or the "
+                                        "projection with vr_set_projection(0))", what,
+                    kName[g.proj]);
+    return fail(VR_ERR_UNSUPPORTED, "%s: the %s projection renders baked planes only (bake the "
+                                    "statistic first, or clear the projection with "
+                                    "vr_set_projection(0))", what, kName[g.proj]);
+}
+
+// the built-in nine entries (K:2323-2326; tf_entry, vr_device.h) as a table, for a
+// projection with no caller's table: the kernel needs no second classifier
+int rtf_upload() {
+    static float rtf[4 * vr::kTfMax] = {0, 0, 0, 0, 1, 0, 0, 1, 1, 0.5f, 0, 1, 1, 1, 0, 1, 0, 1, 0, 1,
+                                        0, 1, 1, 1, 0, 0, 1, 1, 1, 0, 1, 1, 0, 0, 0, 0};
+    static float snap[4 * vr::kTfMax];
+    return table_upload(g.rtf_dev, g.rtf_dirty, g.rtf_stream, rtf, snap, sizeof rtf);
+}
+
+// A frame of P's grid from `plane` (launch_tf_frame's arguments) under the
+// projection: k_march_proj on the bricks themselves, whatever the view -- no plan,
+// no layout copy -- classified through the caller's 1-D table or the built-in one.
+int launch_proj_frame(vr::Params &P, uint32_t nslots, const float *plane, uint64_t psy,
+                      uint64_t psz, bool cross) {
+    const int rc = g.tf_n ? tf_upload() : rtf_upload();
+    if (rc != VR_OK) return rc;
+    P.nb = 1;
+    P.sy = psy;
+    P.sz = psz;
+    const hipError_t e =
+        vr::launch_march_proj(plane, P, g.tf_n ? g.tf_dev : g.rtf_dev, g.tf_n ? g.tf_n : 9, cross,
+                              g.proj, nslots, g.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch(k_march_proj)");
+    (g.tf_n ? g.tf_stream : g.rtf_stream) = g.stream;
+    if (P.tile_cost) g.cost_recorded = true;
+    return VR_OK;
+}
+
+// vr_render's frame under the projection: the plane a table frame reads (tf_plane)
+int render_proj_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, bool dry) {
+    if (g.tf2_nu) return proj_refuse("vr_render");
+    const TfPlane u = tf_plane(desc->query_method);
+    if (!u.pl || !u.pl->buf) return proj_refuse("vr_render");
+    if (dry) return VR_OK;
+    return launch_proj_frame(P, nslots, u.ptr(), u.pl->sy, u.pl->sz, u.cross);
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -1976,6 +2041,7 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     // what a frame costs the issuing thread
     const char *ed = vr::tuning("VR_DRY");
     const bool dry = ed && std::atoi(ed) != 0;
+    if (g.proj) return render_proj_frame(desc, P, nslots, dry);
     if (g.tf_n) return render_tf_frame(desc, P, nslots, dry);
     if (g.tf2_nu) return render_tf2_frame(desc, P, nslots, dry);
     hipError_t e;
@@ -2086,6 +2152,7 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
+    if (g.proj) return proj_refuse("vr_count_footprint");
     if (tf_set()) return tf_refuse("vr_count_footprint");
     if (desc && record_query(desc->query_method))  // no counting instance of their marches
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
@@ -2117,6 +2184,7 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
+    if (g.proj) return proj_refuse("vr_footprint_bytes");
     if (tf_set()) return tf_refuse("vr_footprint_bytes");
     if (desc && record_query(desc->query_method))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
@@ -2578,6 +2646,7 @@ int vr_free_gmm(void) {
 }
 
 int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
+    if (g.proj) return proj_refuse("vr_render_gmm");
     if (tf_set()) return tf_refuse("vr_render_gmm");
     vr::Params P;
     uint32_t nblocks = 0;
@@ -2598,6 +2667,7 @@ int64_t vr_gmm_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_slab *slab) {
+    if (g.proj) return proj_refuse("vr_gmm_count_footprint");
     if (tf_set()) return tf_refuse("vr_gmm_count_footprint");
     vr::Params P;
     uint32_t nblocks = 0;
@@ -2784,6 +2854,7 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     const int plane = set == State::kGmmStats ? desc->query_method - 1 : 0;
     const GmmPlaneSet &ps = kGmmPlaneSets[set];
     const State::GmmStats &b = g.gplanes[set];
+    if (g.proj && g.tf2_nu) return proj_refuse("vr_render_gmm_baked");
     // (under a 2-D table a plane that is not resident is the table's refusal)
     if (!b.buf && g.tf2_nu) return tf_refuse("vr_render_gmm_baked");
     if (!b.buf) return fail(VR_ERR_STATE, "no baked GMM %s (%s first)", ps.planes, ps.bake);
@@ -2811,6 +2882,8 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
     const float *pl = b.buf + (uint64_t)plane * b.plane;
+    if (g.proj)  // a projection: k_march_proj for every method here
+        return launch_proj_frame(P, nslots, pl, b.sy, b.sz, desc->query_method == VR_QUERY_CROSSING);
     if (g.tf_n)  // a custom transfer function: k_march_plane_tf for every method here
         return launch_tf_frame(P, nslots, pl, b.sy, b.sz, desc->query_method == VR_QUERY_CROSSING);
     if (g.tf2_nu)  // a 2-D one: k_march_tf2 on the two planes
@@ -3251,6 +3324,23 @@ int vr_transfer_function(float *rgba, int *n) {
     if (n) *n = g.tf_n;
     return VR_OK;
 }
+
+// ---------------- ray projections ----------
+
+static_assert(VR_PROJ_MAX == vr::kProjMax && VR_PROJ_MIN == vr::kProjMin &&
+                  VR_PROJ_MEAN == vr::kProjMean,
+              "vr.h repeats vr_internal.h's projection modes");
+
+int vr_set_projection(int mode) {
+    if (mode < VR_PROJ_COMPOSITE || mode > VR_PROJ_MEAN)
+        return fail(VR_ERR_ARG, "projection mode %d (0 composite, 1 maximum, 2 minimum, 3 mean)",
+                    mode);
+    if (mode != g.proj) g.volume_epoch++;  // the rays end elsewhere: the tile order starts afresh
+    g.proj = mode;
+    return VR_OK;
+}
+
+int vr_projection(void) { return g.proj; }
 
 // ---------------- 2-D transfer function ----------
 

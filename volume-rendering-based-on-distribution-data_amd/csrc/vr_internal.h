@@ -269,6 +269,16 @@ constexpr int kTf2Max = 1024;
 hipError_t launch_march_tf2(const float *pu, const float *pv, const Params &P, const float4 *table,
                             int nu, int nv, float voff, float vscale, bool cu, bool cv,
                             uint32_t nslots, hipStream_t s);
+// ---- ray projections of a baked plane (vr_project.hip) ----
+// the modes (VR_PROJ_MAX / MIN / MEAN of include/vr.h; 0 composites: no launch here)
+constexpr int kProjMax = 1, kProjMin = 2, kProjMean = 3;
+// k_march_proj: launch_march_plane_tf's plane, table, index widths and kernarg segment;
+// every ray marched to its end with no opacity test, its samples reduced to their
+// maximum, minimum or mean (mode) and that value classified once through the first n
+// entries of the device table, read from global memory.  vr_last_kernel:
+// k_march_proj_max / _min / _mean, M=13 for cross.
+hipError_t launch_march_proj(const float *plane, const Params &P, const float4 *table, int n,
+                             bool cross, int mode, uint32_t nslots, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
