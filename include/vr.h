@@ -1154,6 +1154,54 @@ int vr_transfer_function_2d(float *rgba, int *nu, int *nv, int *method_v, float 
 int vr_set_projection(int mode);
 int vr_projection(void);
 
+/* ---- headlight gradient shading of baked planes ----
+ * A light at the eye that gives the surfaces of a baked-plane frame their shape.
+ * Off (the default) leaves every path exactly as without this state.  On, a ray is
+ * set up, stepped and ended as under a 1-D table (the same positions, the 500-sample
+ * cap, the 0.95 opacity test; d_steps receives the same counts), and at every sample
+ * the gradient of the trilinear interpolant inside the sample's cell is formed from
+ * the 8 corner values s0..s7 the step holds (corner j: x = j & 1, y = j & 2,
+ * z = j & 4; ax, ay, az the footprint's weights; float32, one operation at a time):
+ *     gx = lerp(lerp(s1 - s0, s3 - s2, ay), lerp(s5 - s4, s7 - s6, ay), az)
+ *     gy = lerp(c10 - c00, c11 - c01, az)      c00..c11, c0, c1: the blend's own
+ *     gz = c1 - c0                             intermediates
+ *     G  = (gx nx, gy ny, gz nz)               nx, ny, nz: the volume's dimensions
+ *     c  = |G . d| / sqrt(G . G)  clamped to at most 1; 1 where G . G is not > 0
+ *     p  = c squared shininess_log2 times      (c ^ (2 ^ shininess_log2))
+ * with d the ray's direction, and the table's colour is lit before it is weighted by
+ * its opacity: rgb = rgb * (ambient + diffuse * c) + specular * p.  Alpha is not lit,
+ * so rays end where they end without the light.  For a plane of F (method 13) the
+ * sample stays the crossing combine and the gradient is that of F, the normal of the
+ * probabilistic isosurface.  (ambient, diffuse, specular) = (1, 0, 0) gives the
+ * unlit frame bit for bit.
+ *
+ * vr_set_light: NULL turns the light off.  A coefficient that is not finite or is
+ * negative, or shininess_log2 outside 0..7, is VR_ERR_ARG and the state stays as it
+ * was.  Host state only: no device call, so it may be set before a volume is
+ * resident.  Like the tables it is the caller's: it survives new volumes,
+ * vr_convert_f16, every vr_release_* and freeCudaBuffers; only vr_set_light(NULL)
+ * clears it.  The adaptive tile order is kept: rays have not changed length.
+ * vr_light_state: 1 and *out filled (out may be NULL) if a light is set, 0 if not.
+ *
+ * With the light on, vr_render / render_kernel and vr_render_gmm_baked serve exactly
+ * the frames a 1-D table serves -- the resident baked plane of methods 1/2/3, 4/5/6
+ * and 10-13, of GMM methods 1, 2, 10, 11 and 13 -- classified through the table of
+ * vr_set_transfer_function if one is set, else the built-in nine entries
+ * (k_march_lit; vr_last_kernel: k_march_lit<B=1,M=0 or 13>); tile lists, d_output_f,
+ * d_steps, clipped coverage, VR_TF_WIDE and VR_WG_PER_CU as under the table.
+ * Everything else -- a plane that is not baked, methods 7 and 8/9/0, vr_render_gmm
+ * and slab chains, vr_count_footprint, vr_footprint_bytes,
+ * vr_gmm_count_footprint(_slab), any frame while a 2-D table is set and any frame
+ * while a projection is set (a projection classifies once per ray) -- is
+ * VR_ERR_UNSUPPORTED: bake first, or clear the light.  Nothing falls back to an
+ * unlit frame. */
+typedef struct {
+    float ambient, diffuse, specular;
+    int shininess_log2;
+} vr_light;
+int vr_set_light(const vr_light *l);
+int vr_light_state(vr_light *out);
+
 /* library version string */
 const char *vr_version(void);
 

@@ -81,6 +81,12 @@ class GmmSlab(ctypes.Structure):
     ]
 
 
+class Light(ctypes.Structure):
+    """vr_light (include/vr.h): the headlight of a lit baked-plane frame"""
+    _fields_ = [("ambient", ctypes.c_float), ("diffuse", ctypes.c_float),
+                ("specular", ctypes.c_float), ("shininess_log2", ctypes.c_int)]
+
+
 GMM_RAY_BYTES = 36  # alive-list entry: float sum[4], t, pos[3]; uint32 pixel | samples << 23
 
 
@@ -129,6 +135,7 @@ EXPORTS = [
     "vr_set_transfer_function", "vr_transfer_function",
     "vr_set_transfer_function_2d", "vr_transfer_function_2d",
     "vr_set_projection", "vr_projection",
+    "vr_set_light", "vr_light_state",
 ]
 
 _lib = None
@@ -351,6 +358,10 @@ def load() -> ctypes.CDLL:
     L.vr_set_projection.restype = i32
     L.vr_projection.argtypes = []
     L.vr_projection.restype = i32
+    L.vr_set_light.argtypes = [ctypes.POINTER(Light)]
+    L.vr_set_light.restype = i32
+    L.vr_light_state.argtypes = [ctypes.POINTER(Light)]
+    L.vr_light_state.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

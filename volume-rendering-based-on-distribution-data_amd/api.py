@@ -1063,6 +1063,41 @@ def projection():
     return {v: k for k, v in _PROJ_NAMES.items()}[m]
 
 
+# ------------------- headlight gradient shading
+
+def set_light(ambient=0.3, diffuse=0.7, specular=0.0, shininess=1) -> None:
+    """A light at the eye for frames from baked planes: every classified sample's
+    colour becomes rgb * (ambient + diffuse * c) + specular * c ** shininess, c the
+    cosine between the ray and the gradient of the plane inside the sample's cell
+    (for method 13 the gradient of F, the normal of the probabilistic isosurface).
+    shininess is a power of two from 1 to 128 (ValueError otherwise); the coefficients
+    are finite and >= 0 (VRError otherwise).  set_light(None) turns the light off.
+    Opacity is not lit, so rays keep their lengths; (1, 0, 0) is the unlit frame bit
+    for bit.  Host state only, the caller's like the table: it survives new volumes
+    and freeCudaBuffers.  While the light is on frames come from baked planes, as under
+    a 1-D table; everything else, and any frame while a 2-D table or a projection is
+    set, raises VRError (VR_ERR_UNSUPPORTED)."""
+    L = _lib.load()
+    if ambient is None:
+        check(L.vr_set_light(None))
+        return
+    if (isinstance(shininess, bool) or not isinstance(shininess, (int, np.integer))
+            or shininess < 1 or shininess > 128 or shininess & (shininess - 1)):
+        raise ValueError(f"shininess is a power of two from 1 to 128, got {shininess!r}")
+    light = _lib.Light(float(ambient), float(diffuse), float(specular),
+                       int(shininess).bit_length() - 1)
+    check(L.vr_set_light(ctypes.byref(light)))
+
+
+def light():
+    """The light set, as a dict of ambient, diffuse, specular and shininess; None: off."""
+    out = _lib.Light()
+    if not _lib.load().vr_light_state(ctypes.byref(out)):
+        return None
+    return {"ambient": out.ambient, "diffuse": out.diffuse, "specular": out.specular,
+            "shininess": 1 << out.shininess_log2}
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -1092,5 +1127,6 @@ __all__ = [
     "TF_MAX", "REFERENCE_TF", "set_transfer_function", "transfer_function",
     "TF2_MAX", "set_transfer_function_2d", "transfer_function_2d",
     "PROJ_MAX", "PROJ_MIN", "PROJ_MEAN", "set_projection", "projection",
+    "set_light", "light",
     "VRError", "PAD",
 ]

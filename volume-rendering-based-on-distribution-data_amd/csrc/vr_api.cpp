@@ -156,6 +156,11 @@ struct State {
     float4 *rtf_dev = nullptr;
     bool rtf_dirty = false;
     hipStream_t rtf_stream = nullptr;
+    // headlight gradient shading: off, or the four numbers of
+    // vr_light.  The caller's, like the tables and the projection: tied to no volume.
+    // Host state only; it travels to k_march_lit as a kernel argument.
+    bool light_on = false;
+    vr_light light = {0.0f, 0.0f, 0.0f, 0};
     // 2x2 (x, y) micro-brick copy of an owned 8-bin volume for the quad march
     // of oblique views (ensure_brick, brick_index); nullptr = not made
     float *brick = nullptr;
@@ -2018,6 +2023,55 @@ int render_proj_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots
     return launch_proj_frame(P, nslots, u.ptr(), u.pl->sy, u.pl->sz, u.cross);
 }
 
+// ---- headlight gradient shading of baked planes ----
+
+// What has no lit plane march is refused, never rendered unlit.
+int light_refuse(const char *what) {
+    if (g.proj)
+        return fail(VR_ERR_UNSUPPORTED, "%s: the light shades composited samples, and a "
+                                        "projection classifies once per ray (clear the projection "
+                                        "with vr_set_projection(0), or the light with "
+                                        "vr_set_light(NULL))", what);
+    if (g.tf2_nu)
+        return fail(VR_ERR_UNSUPPORTED, "%s: the light shades one plane, and a 2-D transfer "
+                                        "function is set (clear the table with "
+                                        "vr_set_transfer_function_2d(NULL, 0, 0, 0, 0, 0), or the "
+                                        "light with vr_set_light(NULL))", what);
+    return fail(VR_ERR_UNSUPPORTED, "%s: the light shades frames of baked planes only (bake the "
+                                    "statistic first, or clear the light with "
+                                    "vr_set_light(NULL))", what);
+}
+
+// A frame of P's grid from `plane` (launch_tf_frame's arguments) under the light:
+// k_march_lit on the bricks themselves, whatever the view -- no plan, no layout copy
+// -- classified through the caller's 1-D table or the built-in one (rtf_upload).
+int launch_lit_frame(vr::Params &P, uint32_t nslots, const float *plane, uint64_t psy, uint64_t psz,
+                     bool cross) {
+    const int rc = g.tf_n ? tf_upload() : rtf_upload();
+    if (rc != VR_OK) return rc;
+    P.nb = 1;
+    P.sy = psy;
+    P.sz = psz;
+    const vr::Light L = {g.light.ambient, g.light.diffuse, g.light.specular,
+                         g.light.shininess_log2};
+    const hipError_t e =
+        vr::launch_march_lit(plane, P, g.tf_n ? g.tf_dev : g.rtf_dev, g.tf_n ? g.tf_n : 9, L, cross,
+                             nslots, g.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch(k_march_lit)");
+    (g.tf_n ? g.tf_stream : g.rtf_stream) = g.stream;
+    if (P.tile_cost) g.cost_recorded = true;
+    return VR_OK;
+}
+
+// vr_render's frame under the light: the plane a table frame reads (tf_plane)
+int render_lit_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots, bool dry) {
+    if (g.proj || g.tf2_nu) return light_refuse("vr_render");
+    const TfPlane u = tf_plane(desc->query_method);
+    if (!u.pl || !u.pl->buf) return light_refuse("vr_render");
+    if (dry) return VR_OK;
+    return launch_lit_frame(P, nslots, u.ptr(), u.pl->sy, u.pl->sz, u.cross);
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -2041,6 +2095,7 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     // what a frame costs the issuing thread
     const char *ed = vr::tuning("VR_DRY");
     const bool dry = ed && std::atoi(ed) != 0;
+    if (g.light_on) return render_lit_frame(desc, P, nslots, dry);
     if (g.proj) return render_proj_frame(desc, P, nslots, dry);
     if (g.tf_n) return render_tf_frame(desc, P, nslots, dry);
     if (g.tf2_nu) return render_tf2_frame(desc, P, nslots, dry);
@@ -2152,6 +2207,7 @@ int vr_debug_box_check(uint64_t *d_buf) {
 }
 
 int64_t vr_count_footprint(const vr_render_desc *desc) {
+    if (g.light_on) return light_refuse("vr_count_footprint");
     if (g.proj) return proj_refuse("vr_count_footprint");
     if (tf_set()) return tf_refuse("vr_count_footprint");
     if (desc && record_query(desc->query_method))  // no counting instance of their marches
@@ -2184,6 +2240,7 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_footprint_bytes(const vr_render_desc *desc) {
+    if (g.light_on) return light_refuse("vr_footprint_bytes");
     if (g.proj) return proj_refuse("vr_footprint_bytes");
     if (tf_set()) return tf_refuse("vr_footprint_bytes");
     if (desc && record_query(desc->query_method))
@@ -2646,6 +2703,7 @@ int vr_free_gmm(void) {
 }
 
 int vr_render_gmm(const vr_render_desc *desc, const vr_gmm_slab *slab) {
+    if (g.light_on) return light_refuse("vr_render_gmm");
     if (g.proj) return proj_refuse("vr_render_gmm");
     if (tf_set()) return tf_refuse("vr_render_gmm");
     vr::Params P;
@@ -2667,6 +2725,7 @@ int64_t vr_gmm_count_footprint(const vr_render_desc *desc) {
 }
 
 int64_t vr_gmm_count_footprint_slab(const vr_render_desc *desc, const vr_gmm_slab *slab) {
+    if (g.light_on) return light_refuse("vr_gmm_count_footprint");
     if (g.proj) return proj_refuse("vr_gmm_count_footprint");
     if (tf_set()) return tf_refuse("vr_gmm_count_footprint");
     vr::Params P;
@@ -2854,6 +2913,7 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     const int plane = set == State::kGmmStats ? desc->query_method - 1 : 0;
     const GmmPlaneSet &ps = kGmmPlaneSets[set];
     const State::GmmStats &b = g.gplanes[set];
+    if (g.light_on && (g.proj || g.tf2_nu || !b.buf)) return light_refuse("vr_render_gmm_baked");
     if (g.proj && g.tf2_nu) return proj_refuse("vr_render_gmm_baked");
     // (under a 2-D table a plane that is not resident is the table's refusal)
     if (!b.buf && g.tf2_nu) return tf_refuse("vr_render_gmm_baked");
@@ -2882,6 +2942,8 @@ int vr_render_gmm_baked(const vr_render_desc *desc) {
     int rc = fill_frame_params(&as_plane, v, P, nslots, true);
     if (rc != VR_OK) return rc;
     const float *pl = b.buf + (uint64_t)plane * b.plane;
+    if (g.light_on)  // the light: k_march_lit for every method here
+        return launch_lit_frame(P, nslots, pl, b.sy, b.sz, desc->query_method == VR_QUERY_CROSSING);
     if (g.proj)  // a projection: k_march_proj for every method here
         return launch_proj_frame(P, nslots, pl, b.sy, b.sz, desc->query_method == VR_QUERY_CROSSING);
     if (g.tf_n)  // a custom transfer function: k_march_plane_tf for every method here
@@ -3341,6 +3403,36 @@ int vr_set_projection(int mode) {
 }
 
 int vr_projection(void) { return g.proj; }
+
+// ---------------- headlight gradient shading ----------
+
+static_assert(sizeof(vr_light) == 16 && sizeof(vr::Light) == 16, "the light is 16 bytes");
+
+// Host state only.  The volume epoch is not bumped: opacity is not lit, every ray ends
+// where it ended, and the adaptive tile order recorded without the light stays valid.
+int vr_set_light(const vr_light *l) {
+    if (!l) {
+        g.light_on = false;
+        return VR_OK;
+    }
+    const float k[3] = {l->ambient, l->diffuse, l->specular};
+    static const char *const kName[3] = {"ambient", "diffuse", "specular"};
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(k[i]) || k[i] < 0.0f)
+            return fail(VR_ERR_ARG, "vr_set_light: %s must be finite and >= 0", kName[i]);
+    if (l->shininess_log2 < 0 || l->shininess_log2 > vr::kLightMaxLog2)
+        return fail(VR_ERR_ARG, "vr_set_light: shininess_log2 %d (0 .. %d: the highlight "
+                                "exponent is 2^k)", l->shininess_log2, vr::kLightMaxLog2);
+    g.light = *l;
+    g.light_on = true;
+    return VR_OK;
+}
+
+int vr_light_state(vr_light *out) {
+    if (!g.light_on) return 0;
+    if (out) *out = g.light;
+    return 1;
+}
 
 // ---------------- 2-D transfer function ----------
 

@@ -279,6 +279,20 @@ constexpr int kProjMax = 1, kProjMin = 2, kProjMean = 3;
 // k_march_proj_max / _min / _mean, M=13 for cross.
 hipError_t launch_march_proj(const float *plane, const Params &P, const float4 *table, int n,
                              bool cross, int mode, uint32_t nslots, hipStream_t s);
+// ---- headlight gradient shading of a baked plane (vr_shade.hip) ----
+// the light as the kernel takes it (vr_light of include/vr.h): 16 bytes after
+// launch_march_plane_tf's kernel arguments; k = shininess_log2, 0 .. kLightMaxLog2
+constexpr int kLightMaxLog2 = 7;
+struct Light {
+    float ka, kd, ks;
+    int k;
+};
+// k_march_lit: launch_march_plane_tf's plane, table, LDS and index widths; every
+// classified sample's colour lit by the in-cell gradient of the plane (cross: of F)
+// against the ray, col = col * (ka + kd c) + ks c^(2^k), alpha and so every ray's
+// length untouched.  vr_last_kernel: k_march_lit, M=13 for cross.
+hipError_t launch_march_lit(const float *plane, const Params &P, const float4 *table, int n,
+                            const Light &L, bool cross, uint32_t nslots, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
