@@ -1205,6 +1205,43 @@ int vr_light_state(vr_light *out);
 /* library version string */
 const char *vr_version(void);
 
+/* ---- gradient-magnitude planes of baked planes ----
+ * A boundary axis for frames from baked planes: |grad s| of a resident baked plane s,
+ * baked once per voxel by central differences (one-sided on the volume's faces; an
+ * axis of one voxel contributes 0) and then blended like any other statistic.  With
+ * nx x ny x nz the plane's grid, float32, one operation at a time:
+ *     xm = x > 0 ? x - 1 : 0      xp = x + 1 < nx ? x + 1 : nx - 1      (y, z alike)
+ *     Gx = (s(xp, y, z) - s(xm, y, z)) * (xp - xm == 2 ? nx * 0.5f : nx)
+ *     m  = sqrtf((Gx * Gx + Gy * Gy) + Gz * Gz)
+ * in units of change per unit of the normalised coordinate x / nx (section 25's G).
+ * For method 13 the plane holds F and the gradient is that of F.
+ *
+ * The gradient plane of source method m (1-6, 10-13) is query method
+ * VR_GRADIENT_OF(m) = 32 + m.  vr_render / render_kernel serve it from its plane
+ * wherever a baked plane is served: under the 1-D table, as u or as method_v of the
+ * 2-D table, under a projection, under the light, and with none of these set through
+ * the plane march with the built-in table, as a record query's plane.  It has no
+ * per-step march: with its plane not resident every frame of it is
+ * VR_ERR_UNSUPPORTED (vr_bake_gradient first), and vr_count_footprint /
+ * vr_footprint_bytes of it always are.  GMM planes have no gradient planes:
+ * vr_render_gmm_baked with a gradient method, as the frame's or as method_v, is
+ * VR_ERR_UNSUPPORTED.
+ *
+ * vr_bake_gradient(m): VR_ERR_ARG for an m that is no source, VR_ERR_STATE if m's
+ * plane is not resident (bake it first); nothing to do if the gradient plane is
+ * there; dimensions beyond 65535 are VR_ERR_UNSUPPORTED.  Whatever frees or replaces
+ * a source's plane -- vr_release_stats, the query's vr_release_* and setters, a new
+ * volume, freeCudaBuffers -- frees its gradient plane first, so a plane that is there
+ * was baked from the source that is there.  vr_release_gradient(m) frees the gradient
+ * plane alone.  vr_gradient_info: the plane's device pointer (NULL: not baked), its
+ * length in floats (the layout of the source's plane) and the largest magnitude of
+ * the volume, e.g. for v_scale = 1 / max of a 2-D table. */
+int vr_bake_gradient(int method);
+int vr_release_gradient(int method);
+int vr_gradient_info(int method, const float **d_plane, uint64_t *plane_floats, float *max);
+#define VR_QUERY_GRADIENT 32
+#define VR_GRADIENT_OF(m) (VR_QUERY_GRADIENT + (m))   /* m in 1..6, 10..13 */
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ VR_QUERY_CROSSING = 13
 VR_TF_MAX = 256  # entries of a user-defined transfer function
 VR_PROJ_MAX, VR_PROJ_MIN, VR_PROJ_MEAN = 1, 2, 3  # ray projections (0: composite)
 VR_TF2_MAX = 1024  # entries (nu * nv) of a 2-D one
+VR_QUERY_GRADIENT = 32  # + a source method (1-6, 10-13): its gradient-magnitude plane
 
 
 class VRError(RuntimeError):
@@ -136,6 +137,7 @@ EXPORTS = [
     "vr_set_transfer_function_2d", "vr_transfer_function_2d",
     "vr_set_projection", "vr_projection",
     "vr_set_light", "vr_light_state",
+    "vr_bake_gradient", "vr_release_gradient", "vr_gradient_info",
 ]
 
 _lib = None
@@ -362,6 +364,12 @@ def load() -> ctypes.CDLL:
     L.vr_set_light.restype = i32
     L.vr_light_state.argtypes = [ctypes.POINTER(Light)]
     L.vr_light_state.restype = i32
+    L.vr_bake_gradient.argtypes = [i32]
+    L.vr_bake_gradient.restype = i32
+    L.vr_release_gradient.argtypes = [i32]
+    L.vr_release_gradient.restype = i32
+    L.vr_gradient_info.argtypes = [i32, vp, vp, vp]
+    L.vr_gradient_info.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

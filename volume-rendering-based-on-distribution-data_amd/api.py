@@ -1098,6 +1098,45 @@ def light():
             "shininess": 1 << out.shininess_log2}
 
 
+# ------------------- gradient-magnitude planes
+
+GRADIENT = _lib.VR_QUERY_GRADIENT
+
+
+def gradient_of(m: int) -> int:
+    """The query method of the gradient-magnitude plane of source method m (1-6,
+    10-13): GRADIENT + m.  Frames of it come from the plane bake_gradient(m) makes,
+    wherever a baked plane is served: under a 1-D table, as the frame's method or as
+    method_v of a 2-D table, under a projection, under the light, or with none of
+    these through the built-in table."""
+    m = int(m)
+    if not (1 <= m <= 6 or 10 <= m <= 13):
+        raise ValueError(f"method {m} has no baked plane to take the gradient of")
+    return GRADIENT + m
+
+
+def bake_gradient(m: int) -> None:
+    """Bake |grad s| of the resident baked plane s of method m into a plane of its own
+    (vr_bake_gradient, synchronous): central differences, one-sided on the volume's
+    faces, per unit of the normalised coordinates.  VRError (VR_ERR_STATE) if m's plane
+    is not baked.  The plane goes when its source's plane goes."""
+    check(_lib.load().vr_bake_gradient(int(m)))
+
+
+def release_gradient(m: int) -> None:
+    """Drop the gradient plane of method m; m's own plane stays."""
+    check(_lib.load().vr_release_gradient(int(m)))
+
+
+def gradient_info(m: int):
+    """(plane_ptr, plane_floats, max) of the gradient plane of method m, max the
+    largest magnitude of the volume; (None, 0, 0.0) if it is not baked."""
+    p, n, mx = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_float()
+    check(_lib.load().vr_gradient_info(int(m), ctypes.addressof(p), ctypes.addressof(n),
+                                       ctypes.addressof(mx)))
+    return p.value, n.value, mx.value
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -1128,5 +1167,6 @@ __all__ = [
     "TF2_MAX", "set_transfer_function_2d", "transfer_function_2d",
     "PROJ_MAX", "PROJ_MIN", "PROJ_MEAN", "set_projection", "projection",
     "set_light", "light",
+    "GRADIENT", "gradient_of", "bake_gradient", "release_gradient", "gradient_info",
     "VRError", "PAD",
 ]

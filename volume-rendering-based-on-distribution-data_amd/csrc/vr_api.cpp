@@ -110,6 +110,14 @@ struct State {
     // it) and qplane[method - 10], the one plane its vr_bake_* made of that state
     // (not baked: the march decodes per step), independent of the other three.
     Planes qplane[4];
+    // Gradient-magnitude planes: one optional plane per source
+    // method (1-6: slots 0-5, 10-13: slots 6-9; grad_slot), baked from the source's
+    // resident plane by vr_bake_gradient and freed before anything frees or replaces
+    // that plane; max: the largest magnitude of the plane
+    struct Grad {
+        Planes p;
+        float max = 0.0f;
+    } grad[10];
     // method 10, weighted bins: the bin weights (qn = 0: none set)
     vr::BinWeights qw = {};
     int qn = 0;
@@ -224,10 +232,34 @@ int hip_fail(hipError_t e, const char *what) {
 
 void release_plane_copies();
 
+// The gradient planes.  grad_slot: the slot of source method m
+// (1-6, 10-13), -1 for any other number; grad_source: the source of gradient method
+// qm (VR_GRADIENT_OF), 0 if qm is none.
+int grad_slot(int m) {
+    if (m >= 1 && m <= 6) return m - 1;
+    if (m >= VR_QUERY_WEIGHTED && m <= VR_QUERY_CROSSING) return m - VR_QUERY_WEIGHTED + 6;
+    return -1;
+}
+
+int grad_source(int qm) { return grad_slot(qm - VR_QUERY_GRADIENT) >= 0 ? qm - VR_QUERY_GRADIENT : 0; }
+
+// Frees a gradient plane (vr_release_gradient; before its source's plane goes).  A
+// tile order learned on it is not reused.
+void release_grad(int slot) {
+    State::Grad &gd = g.grad[slot];
+    if (gd.p.buf) {
+        (void)hipFree(gd.p.buf);
+        g.volume_epoch++;
+    }
+    gd = State::Grad();
+}
+
 // Frees a baked plane of a record query (vr_release_*; with the records' other
 // planes; on any call that sets or clears the state it was baked from).  A tile
 // order learned on the plane march is not reused.
 void release_planes(State::Planes &p) {
+    for (int i = 0; i < 4; i++)  // a query's plane: its gradient plane goes first
+        if (&p == &g.qplane[i]) release_grad(6 + i);
     if (p.buf) {
         (void)hipFree(p.buf);
         g.volume_epoch++;
@@ -241,11 +273,13 @@ State::Planes &query_plane(int method) { return g.qplane[method - VR_QUERY_WEIGH
 void release_stats() {
     release_plane_copies();  // copies of the planes go with them
     for (State::Planes &p : g.qplane) release_planes(p);  // derived from the same records
+    for (int m = 1; m <= 3; m++) release_grad(grad_slot(m));
     if (g.stats.buf) (void)hipFree(g.stats.buf);
     g.stats = State::Planes();
 }
 
 void release_cstats() {
+    for (int m = 4; m <= 6; m++) release_grad(grad_slot(m));
     if (g.cstats.buf) (void)hipFree(g.cstats.buf);
     g.cstats = State::Planes();
 }
@@ -479,6 +513,12 @@ int query_ready(const RecordQuery &q) {
 int check_method(int m) {
     if (m == 1 || m == 2 || m == 3 || m == 7 || m == 4 || m == 5 || m == 6) return VR_OK;
     if (const RecordQuery *q = record_query(m)) return query_ready(*q);
+    if (const int src = grad_source(m)) {  // a gradient method has no per-step march
+        if (!g.grad[grad_slot(src)].p.buf)
+            return fail(VR_ERR_UNSUPPORTED, "queryMethod %d renders the gradient plane of method %d "
+                                            "only: vr_bake_gradient(%d) first", m, src, src);
+        return VR_OK;
+    }
     if (is_flex_method(m)) {
         if (!g.flex.blocks)
             return fail(VR_ERR_STATE,
@@ -801,7 +841,14 @@ int fill_frame_params(const vr_render_desc *d, const FrameVol &v, vr::Params &P,
 int fill_params(const vr_render_desc *d, vr::Params &P, uint32_t &nslots,
                 bool for_render = false) {
     if (!d) return fail(VR_ERR_ARG, "null render descriptor");
-    const bool codec = d->query_method >= 4 && d->query_method <= 6;
+    // a gradient method: its plane or a refusal, and the grid of its source's family
+    // (a resident gradient plane has a resident source, so a resident volume)
+    const int gsrc = grad_source(d->query_method);
+    if (gsrc) {
+        const int rc = check_method(d->query_method);
+        if (rc != VR_OK) return rc;
+    }
+    const bool codec = (d->query_method >= 4 && d->query_method <= 6) || (gsrc >= 4 && gsrc <= 6);
     if (codec && !g.cb)
         return fail(VR_ERR_STATE, "queryMethod %d needs a codec volume (initCuda's codebook / "
                                   "vr_init_codec)", d->query_method);
@@ -1926,6 +1973,10 @@ TfPlane tf_plane(int qm) {
         t.pl = &query_plane(qm);
         t.cross = q->cross_plane;
         t.family = 0;
+    } else if (const int src = grad_source(qm)) {
+        // the gradient plane of src, of src's family; |grad F| is blended, not combined
+        t.pl = &g.grad[grad_slot(src)].p;
+        t.family = src >= 4 && src <= 6 ? 1 : 0;
     }
     return t;
 }
@@ -2072,6 +2123,12 @@ int render_lit_frame(const vr_render_desc *desc, vr::Params &P, uint32_t nslots,
     return launch_lit_frame(P, nslots, u.ptr(), u.pl->sy, u.pl->sz, u.cross);
 }
 
+// A gradient method has no per-step march, so nothing to count.
+int grad_refuse(const char *what) {
+    return fail(VR_ERR_UNSUPPORTED, "%s: a gradient method renders its baked plane only "
+                                    "(vr_bake_gradient) and has no per-step march to count", what);
+}
+
 // One frame of vr_render / render_kernel; clip_w x clip_h is the top-left
 // rectangle of pixels the launch covers (render_kernel's gridSize x blockSize,
 // K:2397 + K:282-286; the whole image otherwise).
@@ -2104,6 +2161,13 @@ int render_frame(const vr_render_desc *desc, uint32_t clip_w, uint32_t clip_h) {
     if (is_flex_method(qm)) {
         if (dry) return VR_OK;
         e = vr::launch_march_flex(qm, P, nslots, g.stream);
+    } else if (grad_source(qm)) {
+        // a gradient plane (resident: check_method) under the built-in table, as a
+        // record query's plane
+        if (dry) return VR_OK;
+        const TfPlane u = tf_plane(qm);
+        rc = launch_plane_frame(desc, P, nslots, u.ptr(), u.pl->sy, u.pl->sz, e);
+        if (rc != VR_OK) return rc;
     } else if (qm >= 4 && qm <= 6 && !g.cstats.buf) {
         if (dry) return VR_OK;
         // the one-lane codec march of a row-aligned view: a 16x4 pixel block per
@@ -2210,6 +2274,7 @@ int64_t vr_count_footprint(const vr_render_desc *desc) {
     if (g.light_on) return light_refuse("vr_count_footprint");
     if (g.proj) return proj_refuse("vr_count_footprint");
     if (tf_set()) return tf_refuse("vr_count_footprint");
+    if (desc && grad_source(desc->query_method)) return grad_refuse("vr_count_footprint");
     if (desc && record_query(desc->query_method))  // no counting instance of their marches
         return fail(VR_ERR_UNSUPPORTED, "footprint count is defined for methods 1/2/3");
     vr::Params P;
@@ -2243,6 +2308,7 @@ int64_t vr_footprint_bytes(const vr_render_desc *desc) {
     if (g.light_on) return light_refuse("vr_footprint_bytes");
     if (g.proj) return proj_refuse("vr_footprint_bytes");
     if (tf_set()) return tf_refuse("vr_footprint_bytes");
+    if (desc && grad_source(desc->query_method)) return grad_refuse("vr_footprint_bytes");
     if (desc && record_query(desc->query_method))
         return fail(VR_ERR_UNSUPPORTED, "footprint bytes are defined for methods 1-6");
     vr::Params P;
@@ -3449,9 +3515,11 @@ int vr_set_transfer_function_2d(const float *rgba, int nu, int nv, int method_v,
         return fail(VR_ERR_ARG, "a 2-D transfer function of %d x %d entries (1 .. 256 each, %d in "
                     "all)", nu, nv, VR_TF2_MAX);
     const bool mv_ok = (method_v >= 1 && method_v <= 6) ||
-                       (method_v >= VR_QUERY_WEIGHTED && method_v <= VR_QUERY_CROSSING);
+                       (method_v >= VR_QUERY_WEIGHTED && method_v <= VR_QUERY_CROSSING) ||
+                       grad_source(method_v);
     if (!mv_ok)
-        return fail(VR_ERR_ARG, "method_v %d has no baked plane (1-6, 10-13)", method_v);
+        return fail(VR_ERR_ARG, "method_v %d has no baked plane (1-6, 10-13, or the gradient "
+                                "plane of one of those: 32 + its number)", method_v);
     if (!std::isfinite(v_offset) || !std::isfinite(v_scale))
         return fail(VR_ERR_ARG, "v_offset / v_scale is not finite");
     const int n = nu * nv;
@@ -3484,6 +3552,84 @@ int vr_transfer_function_2d(float *rgba, int *nu, int *nv, int *method_v, float 
         if (v_offset) *v_offset = g.tf2_voff;
         if (v_scale) *v_scale = g.tf2_vscale;
     }
+    return VR_OK;
+}
+
+// ---------------- gradient-magnitude planes ----------
+
+// The plane of |grad s| of the resident plane s of source method `method`, by
+// k_bake_grad, and its maximum.  A plane that is there was baked from this source
+// (whatever frees or replaces the source frees it first): nothing to do.
+int vr_bake_gradient(int method) {
+    const int slot = grad_slot(method);
+    if (slot < 0)
+        return fail(VR_ERR_ARG, "vr_bake_gradient: method %d has no baked plane (1-6, 10-13)",
+                    method);
+    const TfPlane s = tf_plane(method);
+    if (!s.pl->buf) {
+        const RecordQuery *q = record_query(method);
+        return fail(VR_ERR_STATE, "vr_bake_gradient(%d): the plane of method %d is not resident "
+                                  "(%s first)", method, method,
+                    q ? q->bake : "basicDataProcessing / vr_bake_stats");
+    }
+    State::Grad &gd = g.grad[slot];
+    if (gd.p.buf) return VR_OK;
+    vr::Params P;
+    std::memset(&P, 0, sizeof P);
+    if (s.family == 1) {
+        P.nx = g.cnx; P.ny = g.cny; P.nz = g.cnz;
+    } else {
+        P.nx = g.nx; P.ny = g.ny; P.nz = g.nz;
+    }
+    P.nb = 1;
+    uint32_t *d_max = nullptr;  // the maximum's bits: folded by the kernel, read back below
+    VR_HIP(hipMalloc(&d_max, sizeof(uint32_t)));
+    State::Planes p;
+    int rc = VR_OK;
+    hipError_t e = hipMemsetAsync(d_max, 0, sizeof(uint32_t), g.stream);
+    if (e != hipSuccess) rc = hip_fail(e, "vr_bake_gradient");
+    if (rc == VR_OK)
+        rc = bake_planes(p, 1, P, "vr_bake_gradient(k_bake_grad)", "gradient planes",
+                         [&](float *out, uint64_t, uint64_t psy, uint64_t psz) {
+                             // (the planes of one grid share one brick layout)
+                             if (psy != s.pl->sy || psz != s.pl->sz) return hipErrorInvalidValue;
+                             return vr::launch_bake_grad(s.ptr(), out, psy, psz, P.nx, P.ny, P.nz,
+                                                         d_max, g.stream);
+                         });
+    uint32_t bits = 0;
+    if (rc == VR_OK) {  // (bake_planes has drained the stream)
+        e = hipMemcpy(&bits, d_max, sizeof bits, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            (void)hipFree(p.buf);
+            rc = hip_fail(e, "vr_bake_gradient");
+        }
+    }
+    (void)hipFree(d_max);
+    if (rc != VR_OK) return rc;
+    gd.p = p;
+    std::memcpy(&gd.max, &bits, sizeof bits);
+    g.volume_epoch++;  // as bake_query: a tile order learned without the plane is not reused
+    return VR_OK;
+}
+
+int vr_release_gradient(int method) {
+    const int slot = grad_slot(method);
+    if (slot < 0)
+        return fail(VR_ERR_ARG, "vr_release_gradient: method %d has no baked plane (1-6, 10-13)",
+                    method);
+    release_grad(slot);
+    return VR_OK;
+}
+
+int vr_gradient_info(int method, const float **d_plane, uint64_t *plane_floats, float *max) {
+    const int slot = grad_slot(method);
+    if (slot < 0)
+        return fail(VR_ERR_ARG, "vr_gradient_info: method %d has no baked plane (1-6, 10-13)",
+                    method);
+    const State::Grad &gd = g.grad[slot];
+    if (d_plane) *d_plane = gd.p.buf;
+    if (plane_floats) *plane_floats = gd.p.floats;
+    if (max) *max = gd.max;
     return VR_OK;
 }
 

@@ -293,6 +293,15 @@ struct Light {
 // length untouched.  vr_last_kernel: k_march_lit, M=13 for cross.
 hipError_t launch_march_lit(const float *plane, const Params &P, const float4 *table, int n,
                             const Light &L, bool cross, uint32_t nslots, hipStream_t s);
+// ---- gradient-magnitude planes of baked planes (vr_gradient.hip) ----
+// k_bake_grad: the central-difference gradient magnitude (one-sided on the faces, in
+// units of the normalised coordinates x / nx, y / ny, z / nz) of every voxel of the
+// plane src into the plane out, both one float per voxel in 16 x 2 x 1 bricks of
+// plane_pitches(nx, ny) = (psy, psz), aprons filled and empty slots +0; the unsigned
+// maximum of the magnitudes' bits is folded into the zeroed device word max_bits.
+// launch_plane8's limits: a dimension beyond 65535 is hipErrorInvalidValue.
+hipError_t launch_bake_grad(const float *src, float *out, uint64_t psy, uint64_t psz, int nx,
+                            int ny, int nz, uint32_t *max_bits, hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
