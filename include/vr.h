@@ -1205,6 +1205,49 @@ int vr_light_state(vr_light *out);
 /* library version string */
 const char *vr_version(void);
 
+/* ---- value ranges and histograms of baked planes ----
+ * What a window (transfer_offset / transfer_scale, v_offset / v_scale) and a table are
+ * designed from: the value range of a resident baked plane, and the 1-D histogram of
+ * one plane or the joint 2-D histogram of two planes of one volume, binned exactly
+ * into the cells of the table a frame will use.  A method is whatever has a baked
+ * plane: 1-6, 10-13 and VR_GRADIENT_OF(m); for method 13 the plane holds F and the
+ * figures are those of F.  box: six ints x0, x1, y0, y1, z0, z1, the voxels
+ * [x0, x1) x [y0, y1) x [z0, z1) of the plane's grid; NULL: the whole volume.
+ *
+ * The bin of plane value s under the window (offset, scale) of an axis of n entries,
+ * float32, one operation at a time:
+ *     x = (s - offset) * scale
+ *     i = min((int)floorf(clamp01(x) * (float)n), n - 1)      clamp01(NaN) = 0
+ * the texel cell [i / n, (i + 1) / n) of table entry i, around the coordinate
+ * (i + 0.5) / n at which the table's linear filter returns entry i alone.  Values
+ * outside the window land in the edge bins, as the table clamps them; a NaN lands in
+ * bin 0.  counts[j * nu + i] (u fastest, the 2-D table's order) is the number of
+ * voxels of the box with u bin i of nu and v bin j of nv; without a v plane
+ * (method_v 0) nv is 1.  Every voxel of the box is counted once -- the copies and the
+ * padding of the brick layout never -- so the counts sum to the box's voxels.  A
+ * histogram counts voxels; a frame classifies samples interpolated between them.
+ *
+ * vr_plane_range: the minimum and maximum over the box's voxels that are not NaN and
+ * the number that are (any of the three pointers may be NULL), ordered by bit pattern
+ * so that -0 < +0; if every voxel is NaN, min and max are NaN (0x7FC00000).
+ *
+ * Both calls are synchronous on the library's stream, run one kernel (k_plane_range,
+ * k_plane_hist), keep nothing on the device and change no state: tables, projection,
+ * light and planes are as before.  VR_ERR_ARG: a method that names no plane; nu or
+ * nv < 1 or nu * nv > VR_HIST_MAX; method_v 0 with nv != 1; a window that is not
+ * finite; a box that is empty or leaves the grid; counts NULL.  VR_ERR_STATE: a plane
+ * that is not resident (the message names its bake).  VR_ERR_UNSUPPORTED: u and v
+ * planes of different volumes (record and codec), as the 2-D table refuses them, and
+ * dimensions beyond 65535.  vr_plane_kernel_ms: the time of the last such kernel by
+ * HIP events, for measurements. */
+#define VR_HIST_MAX 16384
+int vr_plane_range(int method, const int *box /* 6 ints or NULL */,
+                   float *min, float *max, uint64_t *n_nan);
+int vr_plane_histogram(int method_u, float u_offset, float u_scale, int nu,
+                       int method_v /* 0: none */, float v_offset, float v_scale, int nv,
+                       const int *box, uint64_t *counts /* host, nu * nv */);
+int vr_plane_kernel_ms(float *ms);
+
 /* ---- gradient-magnitude planes of baked planes ----
  * A boundary axis for frames from baked planes: |grad s| of a resident baked plane s,
  * baked once per voxel by central differences (one-sided on the volume's faces; an

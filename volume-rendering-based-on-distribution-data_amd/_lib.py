@@ -31,6 +31,7 @@ VR_TF_MAX = 256  # entries of a user-defined transfer function
 VR_PROJ_MAX, VR_PROJ_MIN, VR_PROJ_MEAN = 1, 2, 3  # ray projections (0: composite)
 VR_TF2_MAX = 1024  # entries (nu * nv) of a 2-D one
 VR_QUERY_GRADIENT = 32  # + a source method (1-6, 10-13): its gradient-magnitude plane
+VR_HIST_MAX = 16384  # bins (nu * nv) of a plane histogram
 
 
 class VRError(RuntimeError):
@@ -138,6 +139,7 @@ EXPORTS = [
     "vr_set_projection", "vr_projection",
     "vr_set_light", "vr_light_state",
     "vr_bake_gradient", "vr_release_gradient", "vr_gradient_info",
+    "vr_plane_range", "vr_plane_histogram", "vr_plane_kernel_ms",
 ]
 
 _lib = None
@@ -370,6 +372,12 @@ def load() -> ctypes.CDLL:
     L.vr_release_gradient.restype = i32
     L.vr_gradient_info.argtypes = [i32, vp, vp, vp]
     L.vr_gradient_info.restype = i32
+    L.vr_plane_range.argtypes = [i32, vp, vp, vp, vp]
+    L.vr_plane_range.restype = i32
+    L.vr_plane_histogram.argtypes = [i32, f32, f32, i32, i32, f32, f32, i32, vp, vp]
+    L.vr_plane_histogram.restype = i32
+    L.vr_plane_kernel_ms.argtypes = [vp]
+    L.vr_plane_kernel_ms.restype = i32
     L.vr_bake_stats.argtypes = []
     L.vr_bake_stats.restype = i32
     L.vr_release_stats.argtypes = []

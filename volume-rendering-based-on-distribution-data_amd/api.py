@@ -1137,6 +1137,76 @@ def gradient_info(m: int):
     return p.value, n.value, mx.value
 
 
+# ------------------- value ranges and histograms of baked planes
+
+HIST_MAX = _lib.VR_HIST_MAX
+
+
+def _box(box):
+    """box as six C ints (x0, x1, y0, y1, z0, z1), or None: the whole volume"""
+    if box is None:
+        return None
+    b = [int(v) for v in np.asarray(box).ravel()]
+    if len(b) != 6:
+        raise ValueError("a box is (x0, x1, y0, y1, z0, z1)")
+    return (ctypes.c_int * 6)(*b)
+
+
+def plane_range(method: int, box=None):
+    """(min, max, n_nan) of the resident baked plane of `method` (1-6, 10-13 or
+    gradient_of(m)) over box = (x0, x1, y0, y1, z0, z1) in voxels, None: the whole
+    volume (vr_plane_range, synchronous).  min and max are numpy.float32 over the voxels
+    that are not NaN, -0 below +0; NaN if every voxel is NaN.  n_nan counts those."""
+    lo, hi, n = ctypes.c_float(), ctypes.c_float(), ctypes.c_uint64()
+    b = _box(box)
+    check(_lib.load().vr_plane_range(int(method), ctypes.addressof(b) if b else None,
+                                     ctypes.addressof(lo), ctypes.addressof(hi),
+                                     ctypes.addressof(n)))
+    return np.float32(lo.value), np.float32(hi.value), n.value
+
+
+def plane_window(method: int, box=None):
+    """(offset, scale) that spreads the plane's values over a table: offset = min and
+    scale = 1 / (max - min) in float32, 1.0 when max <= min, as transfer_offset /
+    transfer_scale or v_offset / v_scale."""
+    lo, hi, _ = plane_range(method, box)
+    if not hi > lo:
+        return float(lo), 1.0
+    with np.errstate(all="ignore"):
+        return float(lo), float(np.float32(1) / np.float32(hi - lo))
+
+
+def plane_histogram(method_u: int, nu: int, window_u=None, method_v: Optional[int] = None,
+                    nv: int = 1, window_v=None, box=None) -> np.ndarray:
+    """The histogram of the resident plane of method_u over nu bins, or with method_v the
+    joint histogram of the two planes over nv x nu bins, of the voxels of `box` (None:
+    the whole volume): numpy.uint64 of shape (nv, nu), bin [j, i] the cell of entry
+    (j, i) of the table a frame under the same windows uses (vr_plane_histogram,
+    synchronous).  A window is (offset, scale); None: plane_window of that plane and
+    box.  Values outside a window count in its edge bins, a NaN in bin 0."""
+    wu = plane_window(method_u, box) if window_u is None else window_u
+    wv = (0.0, 1.0)
+    if method_v is not None:
+        wv = plane_window(method_v, box) if window_v is None else window_v
+    nu, nv = int(nu), int(nv)
+    # (bin counts the library refuses reach it with one word to write nothing into)
+    ok = nu >= 1 and nv >= 1 and nu * nv <= HIST_MAX
+    counts = np.zeros((nv, nu) if ok else (1, 1), dtype=np.uint64)
+    b = _box(box)
+    check(_lib.load().vr_plane_histogram(
+        int(method_u), float(wu[0]), float(wu[1]), int(nu),
+        0 if method_v is None else int(method_v), float(wv[0]), float(wv[1]), int(nv),
+        ctypes.addressof(b) if b else None, counts.ctypes.data))
+    return counts
+
+
+def plane_kernel_ms() -> float:
+    """HIP-event time in ms of the kernel of the last plane_range / plane_histogram"""
+    ms = ctypes.c_float()
+    check(_lib.load().vr_plane_kernel_ms(ctypes.addressof(ms)))
+    return ms.value
+
+
 def version() -> str:
     return _lib.load().vr_version().decode()
 
@@ -1168,5 +1238,6 @@ __all__ = [
     "PROJ_MAX", "PROJ_MIN", "PROJ_MEAN", "set_projection", "projection",
     "set_light", "light",
     "GRADIENT", "gradient_of", "bake_gradient", "release_gradient", "gradient_info",
+    "HIST_MAX", "plane_range", "plane_window", "plane_histogram", "plane_kernel_ms",
     "VRError", "PAD",
 ]

@@ -198,6 +198,8 @@ struct State {
     // released, so an order learned on old data is not reused (the order is a
     // scheduling hint only: any order renders the same image)
     uint32_t volume_epoch = 0;
+    // HIP-event time of the kernel of the last vr_plane_range / vr_plane_histogram
+    float plane_ms = 0.0f;
 };
 
 State g;
@@ -3630,6 +3632,188 @@ int vr_gradient_info(int method, const float **d_plane, uint64_t *plane_floats, 
     if (d_plane) *d_plane = gd.p.buf;
     if (plane_floats) *plane_floats = gd.p.floats;
     if (max) *max = gd.max;
+    return VR_OK;
+}
+
+// ---------------- value ranges and histograms of baked planes ----
+
+}  // extern "C"
+
+namespace {
+
+// A resident plane for vr_plane_range / vr_plane_histogram: tf_plane's, or a refusal
+// (VR_ERR_ARG: the method names no plane; VR_ERR_STATE: not resident, with its bake),
+// and the grid of its family.
+int stat_plane(const char *what, const char *arg, int method, TfPlane &t, int (&dims)[3]) {
+    t = tf_plane(method);
+    if (!t.pl)
+        return fail(VR_ERR_ARG, "%s: %s %d has no baked plane (1-6, 10-13, or the gradient plane "
+                                "of one of those: 32 + its number)", what, arg, method);
+    if (!t.pl->buf) {
+        if (const int src = grad_source(method))
+            return fail(VR_ERR_STATE, "%s: the gradient plane of method %d is not resident "
+                                      "(vr_bake_gradient(%d) first)", what, src, src);
+        const RecordQuery *q = record_query(method);
+        return fail(VR_ERR_STATE, "%s: the plane of method %d is not resident (%s first)", what,
+                    method, q ? q->bake : "basicDataProcessing / vr_bake_stats");
+    }
+    dims[0] = t.family == 1 ? g.cnx : g.nx;
+    dims[1] = t.family == 1 ? g.cny : g.ny;
+    dims[2] = t.family == 1 ? g.cnz : g.nz;
+    if (dims[0] > 65535 || dims[1] > 65535 || dims[2] > 65535)
+        return fail(VR_ERR_UNSUPPORTED, "%s: a grid of %d x %d x %d voxels (65535 at most along "
+                                        "an axis)", what, dims[0], dims[1], dims[2]);
+    return VR_OK;
+}
+
+// what a box must be whatever the grid: three non-empty ranges of non-negative voxels
+int box_sane(const char *what, const int *box) {
+    if (box)
+        for (int a = 0; a < 3; a++)
+            if (box[2 * a] < 0 || box[2 * a] >= box[2 * a + 1])
+                return fail(VR_ERR_ARG, "%s: the box [%d, %d) x [%d, %d) x [%d, %d) is empty or "
+                                        "starts below 0", what, box[0], box[1], box[2], box[3],
+                            box[4], box[5]);
+    return VR_OK;
+}
+
+// box (NULL: the whole grid) as six ints inside the grid, or VR_ERR_ARG
+int box_in_grid(const char *what, const int *box, const int (&dims)[3], int (&out)[6]) {
+    for (int a = 0; a < 3; a++) {
+        out[2 * a] = box ? box[2 * a] : 0;
+        out[2 * a + 1] = box ? box[2 * a + 1] : dims[a];
+        if (out[2 * a + 1] > dims[a])
+            return fail(VR_ERR_ARG, "%s: the box [%d, %d) x [%d, %d) x [%d, %d) leaves the grid of "
+                                    "%d x %d x %d voxels", what, box[0], box[1], box[2], box[3],
+                        box[4], box[5], dims[0], dims[1], dims[2]);
+    }
+    return VR_OK;
+}
+
+// Runs `launch` on the library's stream between two events and waits for it; the
+// kernel's time goes to g.plane_ms (vr_plane_kernel_ms).
+template <typename Launch>
+int timed_launch(const char *what, Launch launch) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, g.stream);
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(e1, g.stream);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e != hipSuccess) (void)hipStreamSynchronize(g.stream);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e != hipSuccess) return hip_fail(e, what);
+    g.plane_ms = ms;
+    return VR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_plane_range(int method, const int *box, float *min, float *max, uint64_t *n_nan) {
+    const char *const what = "vr_plane_range";
+    int rc = box_sane(what, box);
+    if (rc != VR_OK) return rc;
+    TfPlane t;
+    int dims[3], b[6];
+    if ((rc = stat_plane(what, "method", method, t, dims)) != VR_OK) return rc;
+    if ((rc = box_in_grid(what, box, dims, b)) != VR_OK) return rc;
+    // the scratch: the two keys, preset to the identities of min and max, and the count
+    struct Words {
+        uint32_t keys[2];
+        unsigned long long nan;
+    } h = {{0xFFFFFFFFu, 0u}, 0ull}, *d = nullptr;
+    VR_HIP(hipMalloc(&d, sizeof h));
+    hipError_t e = hipMemcpyAsync(d, &h, sizeof h, hipMemcpyHostToDevice, g.stream);
+    rc = e == hipSuccess ? VR_OK : hip_fail(e, what);
+    if (rc == VR_OK)
+        rc = timed_launch("vr_plane_range(k_plane_range)", [&] {
+            return vr::launch_plane_range(t.ptr(), t.pl->sy, t.pl->sz, dims[0], dims[1], dims[2], b,
+                                          d->keys, &d->nan, g.stream);
+        });
+    if (rc == VR_OK) {  // (timed_launch has drained the stream)
+        e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, what);
+    } else {
+        (void)hipStreamSynchronize(g.stream);
+    }
+    (void)hipFree(d);
+    if (rc != VR_OK) return rc;
+    uint32_t lo = 0x7FC00000u, hi = 0x7FC00000u;  // every voxel NaN: NaN
+    if (h.keys[0] <= h.keys[1]) {
+        lo = (h.keys[0] & 0x80000000u) ? h.keys[0] ^ 0x80000000u : ~h.keys[0];
+        hi = (h.keys[1] & 0x80000000u) ? h.keys[1] ^ 0x80000000u : ~h.keys[1];
+    }
+    if (min) std::memcpy(min, &lo, sizeof lo);
+    if (max) std::memcpy(max, &hi, sizeof hi);
+    if (n_nan) *n_nan = h.nan;
+    return VR_OK;
+}
+
+int vr_plane_histogram(int method_u, float u_offset, float u_scale, int nu, int method_v,
+                       float v_offset, float v_scale, int nv, const int *box, uint64_t *counts) {
+    const char *const what = "vr_plane_histogram";
+    if (!counts) return fail(VR_ERR_ARG, "%s: counts is null", what);
+    if (nu < 1 || nv < 1 || (int64_t)nu * nv > VR_HIST_MAX)
+        return fail(VR_ERR_ARG, "%s: a histogram of %d x %d bins (1 or more each, %d in all)", what,
+                    nu, nv, VR_HIST_MAX);
+    if (method_v == 0 && nv != 1)
+        return fail(VR_ERR_ARG, "%s: nv = %d without a v plane (method_v 0 takes nv = 1)", what, nv);
+    if (!std::isfinite(u_offset) || !std::isfinite(u_scale) ||
+        (method_v != 0 && (!std::isfinite(v_offset) || !std::isfinite(v_scale))))
+        return fail(VR_ERR_ARG, "%s: a window (offset / scale) is not finite", what);
+    int rc = box_sane(what, box);
+    if (rc != VR_OK) return rc;
+    // both methods name planes, of one family, before either has to be resident
+    const TfPlane named_u = tf_plane(method_u), named_v = method_v ? tf_plane(method_v) : named_u;
+    if (!named_u.pl)
+        return fail(VR_ERR_ARG, "%s: method_u %d has no baked plane (1-6, 10-13, or the gradient "
+                                "plane of one of those: 32 + its number)", what, method_u);
+    if (!named_v.pl)
+        return fail(VR_ERR_ARG, "%s: method_v %d has no baked plane (0: none; 1-6, 10-13, or the "
+                                "gradient plane of one of those: 32 + its number)", what, method_v);
+    if (named_u.family != named_v.family)
+        return fail(VR_ERR_UNSUPPORTED, "%s: methods %d and %d are planes of different volumes (the "
+                                        "record volume's: 1-3, 10-13; the codec volume's: 4-6)",
+                    what, method_u, method_v);
+    TfPlane u, v;
+    int dims[3], b[6];
+    if ((rc = stat_plane(what, "method_u", method_u, u, dims)) != VR_OK) return rc;
+    if (method_v && (rc = stat_plane(what, "method_v", method_v, v, dims)) != VR_OK) return rc;
+    if (method_v && (u.pl->floats != v.pl->floats || u.pl->sy != v.pl->sy || u.pl->sz != v.pl->sz))
+        return fail(VR_ERR_STATE, "the planes of methods %d and %d differ in size or pitches",
+                    method_u, method_v);
+    if ((rc = box_in_grid(what, box, dims, b)) != VR_OK) return rc;
+    const size_t bytes = (size_t)nu * (size_t)nv * sizeof(unsigned long long);
+    unsigned long long *d = nullptr;
+    VR_HIP(hipMalloc(&d, bytes));
+    hipError_t e = hipMemsetAsync(d, 0, bytes, g.stream);
+    rc = e == hipSuccess ? VR_OK : hip_fail(e, what);
+    if (rc == VR_OK)
+        rc = timed_launch("vr_plane_histogram(k_plane_hist)", [&] {
+            return vr::launch_plane_hist(u.ptr(), method_v ? v.ptr() : nullptr, u.pl->sy, u.pl->sz,
+                                         dims[0], dims[1], dims[2], b, u_offset, u_scale, nu,
+                                         v_offset, v_scale, nv, d, g.stream);
+        });
+    if (rc == VR_OK) {  // (timed_launch has drained the stream)
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counts are 64-bit");
+        e = hipMemcpy(counts, d, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, what);
+    } else {
+        (void)hipStreamSynchronize(g.stream);
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+int vr_plane_kernel_ms(float *ms) {
+    if (!ms) return fail(VR_ERR_ARG, "vr_plane_kernel_ms: ms is null");
+    *ms = g.plane_ms;
     return VR_OK;
 }
 

@@ -302,6 +302,26 @@ hipError_t launch_march_lit(const float *plane, const Params &P, const float4 *t
 // launch_plane8's limits: a dimension beyond 65535 is hipErrorInvalidValue.
 hipError_t launch_bake_grad(const float *src, float *out, uint64_t psy, uint64_t psz, int nx,
                             int ny, int nz, uint32_t *max_bits, hipStream_t s);
+// ---- value ranges and histograms of baked planes (vr_histogram.hip) ----
+constexpr int kHistMax = 16384;  // VR_HIST_MAX: bins (nu * nv) of a histogram, 64 KiB of LDS
+// k_plane_hist<V>: the voxels of box = {x0, x1, y0, y1, z0, z1} (inside the grid, not
+// empty) of the plane pu (V = 0: pv NULL, nv 1) or of the planes pu and pv of one grid
+// (V = 1), both in 16 x 2 x 1 bricks of plane_pitches(nx, ny) = (psy, psz), counted
+// into the zeroed device array counts[nv * nu]: counts[j * nu + i] += 1 for a voxel
+// with i = point_axis((u - uoff) * uscale, nu) and j likewise of v; aprons, empty
+// slots and padding are never counted.  k_plane_range: the unsigned minimum and
+// maximum of the monotone keys (bits ^ 0x80000000 for a non-negative pattern, ~bits
+// for a negative one) of the box's voxels that are not NaN into keys[0] / keys[1]
+// (preset to 0xFFFFFFFF / 0), and the number that are NaN added to *n_nan.
+// launch_plane8's limits: a dimension beyond 65535 is hipErrorInvalidValue, as is a
+// box that is empty or leaves the grid, or nu * nv beyond kHistMax.
+hipError_t launch_plane_hist(const float *pu, const float *pv, uint64_t psy, uint64_t psz, int nx,
+                             int ny, int nz, const int *box, float uoff, float uscale, int nu,
+                             float voff, float vscale, int nv, unsigned long long *counts,
+                             hipStream_t s);
+hipError_t launch_plane_range(const float *p, uint64_t psy, uint64_t psz, int nx, int ny, int nz,
+                              const int *box, uint32_t *keys, unsigned long long *n_nan,
+                              hipStream_t s);
 hipError_t launch_logcheck(unsigned long long *cnt, hipStream_t s);
 hipError_t launch_synth(float *vol, const SynthArgs &a, hipStream_t s);
 hipError_t launch_unscatter(const uint32_t *packed, const uint32_t *lists, uint32_t ntiles,
