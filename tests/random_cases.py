@@ -1,6 +1,8 @@
 """Pure case generators of the seeded random sweeps (tests/test_gpu_random.py,
 tests/test_gpu_random_queries.py, tests/test_gpu_random_transfer.py and the CPU
-census tests/test_random_cases.py).
+census tests/test_random_cases.py; at the end of the file PLANE_SWEEPS, the sweeps of
+tests/test_gpu_random_shading.py and tests/test_gpu_random_planes.py with the census
+tests/test_random_planes.py).
 
 No GPU and no library: numpy only.  Every generator maps a seed to a plain dict of
 Python values -- dims, bins or K, dtype, method and query state, W and H, the
@@ -467,3 +469,254 @@ SWEEPS = {"hist": (hist_query_case, 96), "tiles": (hist_tile_case, 24), "f16": (
           "gmm": (gmm_case, 40), "chain": (gmm_chain_case, 16),
           "tf": (tf_case, 56), "tf2": (tf2_case, 72), "tftiles": (tf_tile_case, 16)}
 TF_SWEEPS = ("tf", "tf2", "tftiles")
+
+
+# ---- lit frames, gradient planes, ranges and histograms (tests/test_gpu_random_shading.py,
+# tests/test_gpu_random_planes.py and the CPU census tests/test_random_planes.py) ----
+
+GRADIENT = 32   # VR_QUERY_GRADIENT: method 32 + m is the gradient-magnitude plane of method m
+
+# Nominal range of the gradient magnitude of each source statistic, for draw_window: not a
+# bound.  Derived on the CPU from the reference planes of the lit sweeps' own volumes:
+# ref_gradient.gradient_plane of the tf_plane of every record and codec case of lit_case
+# (48 seeds) and lit_tile_case (8 seeds) whatever plane the case was dealt, the 90th
+# percentile of the finite magnitudes per case, the median of those over the cases of a
+# statistic, rounded to two digits (tests/test_random_planes.py::test_gradient_spans
+# recomputes them and holds each entry within a factor of two).
+SPAN.update({"grad mean": (0.0, 3.1), "grad variance": (0.0, 17.0), "grad entropy": (0.0, 6.0),
+             "grad weights": (0.0, 11.0), "grad range": (0.0, 2.3), "grad quantile": (0.0, 2.5),
+             "grad spread": (0.0, 2.9), "grad distance": (0.0, 4.1), "grad crossing": (0.0, 2.0)})
+
+# (ka, kd, ks, k), k the exponent's log2, dealt by seed % 24: a matte light, diffuse only
+# (ambient 0), a highlight of every exponent 2^0 .. 2^7, ks > 0 with kd = 0, the identity
+# (once in 24: twice in lit_case's 48), coefficients that sum above 1 (colours saturate),
+# and more of the same kinds
+IDENTITY_LIGHT = (1.0, 0.0, 0.0, 0)
+LIT_LIGHTS = ((0.3, 0.7, 0.0, 0), (0.0, 1.0, 0.0, 0), (0.2, 0.5, 0.6, 0), (0.2, 0.5, 0.6, 1),
+              (0.1, 0.6, 0.5, 2), (0.3, 0.4, 0.5, 3), (0.2, 0.5, 0.6, 4), (0.0, 0.7, 0.6, 5),
+              (0.25, 0.5, 0.5, 6), (0.0, 1.0, 1.0, 7), (0.4, 0.0, 0.8, 3), IDENTITY_LIGHT,
+              (0.8, 0.9, 0.7, 2), (0.5, 0.5, 0.0, 0), (0.0, 0.0, 1.0, 1), (0.6, 0.4, 0.3, 5),
+              (0.0, 0.25, 0.75, 0), (0.1, 0.9, 0.0, 0), (1.5, 0.5, 0.25, 6), (0.3, 0.0, 0.7, 7),
+              (0.15, 0.35, 0.5, 4), (0.05, 2.0, 0.0, 0), (0.2, 0.3, 0.5, 2), (0.45, 0.55, 1.0, 1))
+
+
+def _lit_gradient(family, turn):
+    """whether a lit case marches the gradient plane of its method: 12 record cases in
+    28 turns, shifted each round of the seven methods so that every method's gradient
+    plane occurs, 4 codec cases in 8 (methods 5, 4, 6, 4), never a GMM volume"""
+    if family == "records":
+        return (turn + turn // 7) % 7 in (1, 3, 5)
+    return family == "codec" and turn % 8 in (1, 3, 5, 6)
+
+
+def _lit_case(rng, seed, sweep, u, grad, light, wmax, hmax, **more):
+    family, turn = _turn(seed)
+    c = dict(sweep=sweep, seed=seed, u=u, v=None, **more,
+             **_tf_volume(rng, seed, family, turn, (u,)))
+    plane = GRADIENT + u if grad else u
+    if grad:
+        c["stats"][plane] = "grad " + c["stats"][u]
+    c = _tf_rest(rng, seed, c, plane, None, wmax, hmax)
+    if seed % 4 == 2:
+        c["table"] = None   # the built-in nine entries
+    c.update(plane=plane, grad=grad, light=light)
+    return c
+
+
+def lit_case(seed):
+    """a whole frame from a baked plane under a 1-D table and the headlight
+    (k_march_lit).  tf_case's deals -- family, method, dtype, bins or K, edge shapes,
+    table size and kind, negated window, the 1 x 1 frame seen from inside, TF_KNOBS -- and
+    dealt besides: the plane (the method's own or, _lit_gradient, 32 + method), no
+    table (the built-in nine) for one seed in four, the light (LIT_LIGHTS)"""
+    rng = np.random.default_rng(11000 + seed)
+    family, turn = _turn(seed)
+    u = TF_METHODS[family][turn % len(TF_METHODS[family])]
+    return _lit_case(rng, seed, "lit", u, _lit_gradient(family, turn), LIT_LIGHTS[seed % 24],
+                     96, 72)
+
+
+def lit_tile_case(seed):
+    """a lit frame split over 2-8 ranks' tile lists; the method is drawn, the gradient
+    plane dealt to seeds 1 (codec), 4 and 7 (records), the lights are LIT_LIGHTS[1::3]"""
+    rng = np.random.default_rng(11500 + seed)
+    family, _ = _turn(seed)
+    methods = TF_METHODS[family]
+    u = int(methods[int(rng.integers(0, len(methods)))])
+    grad = family != "gmm" and seed % 3 == 1
+    return _lit_case(rng, seed, "littiles", u, grad, LIT_LIGHTS[(3 * seed + 1) % 24], 200, 120,
+                     world=2 + seed % 7)
+
+
+# the sizes at which k_bake_grad's tiles (60 voxels of x plus an apron, 16 rows, 64 slices
+# read ahead four at a time) and the planes' bricks (15 voxels, 2 rows) begin and end
+GRAD_NX = (1, 2, 15, 16, 17, 59, 60, 61, 62, 76, 121)
+GRAD_NY = (1, 2, 3, 15, 16, 17, 18, 33)
+GRAD_NZ = (1, 2, 3, 4, 5, 6, 63, 64, 65, 66, 128, 129)
+PLANE_FAMILIES = (("records", "f32"), ("records", "f16"), ("codec", "f32"))
+PLANE_METHODS = {"records": (1, 2, 3, 10, 11, 12, 13), "codec": (4, 5, 6)}
+
+
+def _plane_volume(rng, seed, dims, family, dtype, nb, methods):
+    """a record or codec volume with the query state of `methods`, in the form the table
+    sweeps' helpers read (test_random_cases.tf_records, tf_plane)"""
+    c = dict(seed=seed, family=family, dims=dims, dtype=dtype, nb=nb)
+    c["queries"], c["stats"] = draw_axis_queries(rng, family, methods, nb, dims, dtype, 0)
+    return c
+
+
+def make_wide(fill, shape):
+    """the float32 values a case's `fill` entry writes over a plane: signed, the
+    magnitudes log-uniform in [2^-20, 2^20], one value in 16 a +0, -0 or a denormal of
+    either sign; nonfinite: +inf, -inf and NaN at three voxels each (fewer in a plane of
+    fewer voxels)"""
+    rng = np.random.default_rng(fill["seed"])
+    n = int(np.prod(shape))
+    a = (np.exp2(rng.uniform(-20, 20, n)) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
+    small = np.array([0, 0x80000000, 1, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x00012345],
+                     np.uint32).view(np.float32)
+    pick = rng.random(n) < 1 / 16
+    a[pick] = small[rng.integers(0, small.size, int(pick.sum()))]
+    if fill["nonfinite"]:
+        where = rng.choice(n, min(n, 9), replace=False)
+        a[where] = np.resize(np.array([np.inf, -np.inf, np.nan], np.float32), where.size)
+    return a.reshape(shape)
+
+
+def grad_case(seed):
+    """one bake of a gradient-magnitude plane (k_bake_grad).  Everything is dealt: the
+    dims from GRAD_NX / GRAD_NY / GRAD_NZ, the source over PLANE_FAMILIES (seed % 3) and
+    the family's methods in turn, the bin count; seeds 3 mod 4 overwrite the source plane
+    with make_wide's values, seeds 7 mod 8 of those plant +-inf and NaN"""
+    rng = np.random.default_rng(12000 + seed)
+    dims = (GRAD_NX[seed % 11], GRAD_NY[(seed + seed // 8) % 8],
+            GRAD_NZ[(seed + 5 * (seed // 12)) % 12])
+    family, dtype = PLANE_FAMILIES[seed % 3]
+    methods = PLANE_METHODS[family]
+    u = methods[(seed // 3) % len(methods)]
+    nb = (4, 8, 2)[(seed // 3) % 3]
+    c = dict(sweep="grad", u=u, v=None, **_plane_volume(rng, seed, dims, family, dtype, nb, (u,)))
+    c["fill"] = None
+    if seed % 4 == 3:
+        c["fill"] = dict(seed=int(rng.integers(1, 1 << 20)), nonfinite=seed % 8 == 7)
+    return c
+
+
+BOX_KINDS = ("whole", "voxel", "x end", "x start", "odd row", "even row", "slice", "inside")
+WINDOW_KINDS = ("full", "default", "drawn", "negated", "zero", "one bin")
+# bin counts by the number of LDS copies they leave room for, R = 32, 16, 8, 4, 2, 1 (nu *
+# nv in (..512], (512, 1024], .. (8192, 16384]): nu of a 1-D call, (nu, nv) of a 2-D one
+STAT_BINS_1D = ((1, 9, 37, 512), (1024, 521, 1000, 600), (2048, 1031, 1500, 2000),
+                (4096, 2049, 3001, 4000), (8192, 4097, 5003, 8000), (16384, 8193, 16381, 12000))
+STAT_BINS_2D = (((1, 1), (16, 8), (4, 3), (32, 16)), ((32, 32), (64, 16), (31, 33), (256, 4)),
+                ((64, 32), (128, 16), (45, 45), (1024, 2)),
+                ((64, 64), (256, 16), (63, 65), (2, 2048)),
+                ((128, 64), (256, 32), (90, 91), (4096, 2)),
+                ((128, 128), (256, 64), (127, 129), (16384, 1)))
+FULL_BINS_1D, FULL_BINS_2D = (1, 5, 9, 16), ((1, 1), (3, 2), (4, 4), (8, 2))
+STAT_VOXELS = 200_000
+
+
+def _span(rng, n):
+    a = int(rng.integers(0, n))
+    return a, int(rng.integers(a + 1, n + 1))
+
+
+def _stat_box(rng, kind, dims, turn):
+    """the box of a stat case: None for the whole volume, else (x0, x1, y0, y1, z0, z1)"""
+    nx, ny, nz = dims
+    (x0, x1), (y0, y1), (z0, z1) = (_span(rng, n) for n in dims)
+    k = int(rng.integers(1, max(nx // 15, 1) + 1))
+    if kind == "whole":
+        return None
+    if kind == "voxel":
+        x1, y1, z1 = x0 + 1, y0 + 1, z0 + 1
+    elif kind == "x end":   # at 15 k, 15 k + 1 and 15 k - 1 in turn; all rows and slices
+        x1 = min(max(15 * k + (0, 1, -1)[turn % 3], 1), nx)
+        x0, y0, y1, z0, z1 = int(rng.integers(0, x1)), 0, ny, 0, nz
+    elif kind == "x start":  # at 15 k and 15 k + 1 in turn; all rows and slices
+        x0 = min(15 * k + turn % 2, nx - 1)
+        x1, y0, y1, z0, z1 = int(rng.integers(x0 + 1, nx + 1)), 0, ny, 0, nz
+    elif kind in ("odd row", "even row"):
+        y0 = 2 * int(rng.integers(0, (ny + 1) // 2))
+        if kind == "odd row" and y0 + 1 < ny:
+            y0 += 1
+        elif kind == "odd row" and y0 > 0:
+            y0 -= 1
+        x0, x1, y1, z0, z1 = 0, nx, y0 + 1, 0, nz
+    elif kind == "slice":
+        x0, x1, y0, y1, z1 = 0, nx, 0, ny, z0 + 1
+    return (x0, x1, y0, y1, z0, z1)
+
+
+def _stat_window(rng, kind, stat, turn):
+    """a window of a stat case: None (the library's default), (offset, scale), or a kind
+    the test resolves on the plane it holds: ("one bin", side) puts every finite value
+    below the window (side 0) or above it (1), ("full",) is the box's own range"""
+    off, scale = draw_window(rng, stat)
+    if kind == "default":
+        return None
+    if kind == "drawn":
+        return (off, scale)
+    if kind == "negated":
+        return _negated(stat, off, scale)
+    if kind == "zero":
+        return (off, 0.0)
+    return ("one bin", turn % 2) if kind == "one bin" else ("full",)
+
+
+def stat_case(seed):
+    """one volume, its planes u and v (v None: a 1-D call), a box, bin counts and
+    windows for plane_range, plane_window and plane_histogram.  Everything that matters
+    is dealt: odd seeds are 2-D calls; with j = seed // 2 the family is PLANE_FAMILIES[j %
+    3], the class of LDS copies (j + j // 6) % 6 and its bin counts STAT_BINS[j // 6]; the
+    planes are the family's methods in turn, as themselves and as gradient planes (1-D:
+    every second; 2-D in turn (a, b), (a, gradient of a), (gradient of a, b), (a, a));
+    the box kind is BOX_KINDS[(seed + seed // 8) % 8]; u's window kind turns through
+    WINDOW_KINDS against the classes, v's is u's where that is `zero` or `one bin` (so
+    that every voxel meets one bin) and one of the other four else; a `full` window of u
+    comes with the few bins of FULL_BINS and the most slices the cap allows, so that it
+    can leave every bin populated; j = 1 mod 4 injects
+    special values into plane u and poisons the slots that are no voxel's home."""
+    rng = np.random.default_rng(12500 + seed)
+    form, j = seed % 2, seed // 2
+    ix, iy, iz = seed % 11, (3 * seed + seed // 8) % 8, (5 * seed + seed // 12) % 12
+    if j % 2 == 1 or j % 6 == 0:   # the most slices the cap allows
+        iz = 11
+    while GRAD_NX[ix] * GRAD_NY[iy] * GRAD_NZ[iz] > STAT_VOXELS:
+        iz = (iz - 1) % 12
+    dims = (GRAD_NX[ix], GRAD_NY[iy], GRAD_NZ[iz])
+    family, dtype = PLANE_FAMILIES[j % 3]
+    methods = PLANE_METHODS[family]
+    t = j // 3
+    a, b = methods[t % len(methods)], methods[(t + 1 + t // 4) % len(methods)]
+    if form == 0:
+        u, v = (GRADIENT + a if t % 2 else a), None
+    else:
+        u, v = ((a, b), (a, GRADIENT + a), (GRADIENT + a, b), (a, a))[t % 4]
+    sources = tuple(dict.fromkeys(m % GRADIENT for m in (u, v) if m is not None))
+    c = dict(sweep="stat", u=u, v=v,
+             **_plane_volume(rng, seed, dims, family, dtype, (4, 8, 2)[t % 3], sources))
+    for m in (u, v):
+        if m is not None and m > GRADIENT:
+            c["stats"][m] = "grad " + c["stats"][m - GRADIENT]
+    cls, turn = (j + j // 6) % 6, j // 6
+    ku = WINDOW_KINDS[(5 * j) % 6]
+    c["nu"], c["nv"] = (STAT_BINS_1D[cls][turn], 1) if form == 0 else STAT_BINS_2D[cls][turn]
+    if ku == "full":   # few enough bins for a linear window to populate them all
+        cls = 0
+        c["nu"], c["nv"] = (FULL_BINS_1D[turn], 1) if form == 0 else FULL_BINS_2D[turn]
+    c["copies"] = 32 >> cls
+    c["box_kind"] = BOX_KINDS[(seed + seed // 8) % 8]
+    c["box"] = _stat_box(rng, c["box_kind"], dims, seed // 8)
+    kv = ku if ku in ("zero", "one bin") else \
+        ("default", "drawn", "negated", "full")[(j + turn) % 4]
+    c["window_kinds"] = (ku, kv if form else None)
+    c["wu"] = _stat_window(rng, ku, c["stats"][u], turn)
+    c["wv"] = _stat_window(rng, kv, c["stats"][v], turn + 1) if form else None
+    c["inject"] = int(rng.integers(1, 1 << 20)) if j % 4 == 1 else None
+    return c
+
+
+PLANE_SWEEPS = {"lit": (lit_case, 48), "littiles": (lit_tile_case, 8), "grad": (grad_case, 24),
+                "stat": (stat_case, 48)}

@@ -33,6 +33,9 @@ f32 = np.float32
 IDENTITY = (1.0, 0.0, 0.0, 0)
 
 
+MUTANTS = ("unscaled", "lit_alpha")
+
+
 def gradient(vals, ax, dims):
     """vals (8, ...) float32 corner values, ax the three _lin results (i0, i1, a) of
     x, y, z, dims (nx, ny, nz) -> (Gx, Gy, Gz): the gradient of the trilinear
@@ -74,19 +77,23 @@ def shade(c, light):
 
 
 def render_plane(F, W, H, m, table, light, blend=ref_crossing.combine, density=0.05,
-                 brightness=1.0, toff=0.0, tscale=1.0, info=None):
+                 brightness=1.0, toff=0.0, tscale=1.0, info=None, mutant=None):
     """ref_crossing.render_plane's triple (packed RGBA8 (H, W) uint32, float RGBA
     (H, W, 4), samples per pixel (H, W), -1 = miss) of the plane F (nz, ny, nx) lit by
     `light`, classified through `table` (None: the built-in nine entries).  info:
-    optional dict, receives samples (taken), flat (taken where g2 > 0 is false) and c
-    (a float32 array of every sample's cosine, in no particular order)."""
+    optional dict, receives samples (taken), clamped (taken in a cell whose footprint
+    the volume's edge clamps along an axis), flat (taken where g2 > 0 is false) and c
+    (a float32 array of every sample's cosine, in no particular order).  mutant: one of
+    MUTANTS, a wrong version a census must be able to tell from the right one (the
+    gradient not scaled by the dims; alpha lit as the colours are)."""
+    assert mutant in (None,) + MUTANTS
     with np.errstate(all="ignore"):
         return _march(np.asarray(F, dtype=np.float32), W, H, m,
                       ref_numpy.TF if table is None else table, light, blend, density, brightness,
-                      toff, tscale, info)
+                      toff, tscale, info, mutant)
 
 
-def _march(F, W, H, m, table, light, blend, density, brightness, toff, tscale, info):
+def _march(F, W, H, m, table, light, blend, density, brightness, toff, tscale, info, mutant=None):
     nz, ny, nx = F.shape
     M = np.asarray(m, dtype=np.float32).reshape(12)
     ys, xs = np.mgrid[0:H, 0:W]
@@ -112,7 +119,7 @@ def _march(F, W, H, m, table, light, blend, density, brightness, toff, tscale, i
     s = np.zeros((H, W, 4), dtype=np.float32)
     n = np.where(hit, 0, -1)
     active = hit.copy()
-    samples = flat = 0
+    samples = flat = clamped = 0
     cs = []
     dims = (nx, ny, nz)
     for i in range(500):
@@ -127,17 +134,20 @@ def _march(F, W, H, m, table, light, blend, density, brightness, toff, tscale, i
             vals.append(F[zi, yi, xi])
         vals = np.stack(vals)
         sample = blend(vals, ax)
-        G = gradient(vals, ax, dims)
+        G = gradient(vals, ax, (1, 1, 1) if mutant == "unscaled" else dims)
         c = cosine(G, d)
         sh, sp = shade(c, light)
         if info is not None:
             g2 = (G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]
+            edge = (ax[0][0] == ax[0][1]) | (ax[1][0] == ax[1][1]) | (ax[2][0] == ax[2][1])
             samples += int(active.sum())
+            clamped += int((active & edge).sum())
             flat += int((active & ~(g2 > 0)).sum())
             cs.append(c[active])
         col = transfer_table((sample - f32(toff)) * f32(tscale), table)
         rgb = [col[..., k] * sh + sp for k in range(3)]
-        cw = col[..., 3] * f32(density)
+        alpha = col[..., 3] * sh + sp if mutant == "lit_alpha" else col[..., 3]
+        cw = alpha * f32(density)
         col = np.stack([rgb[0] * cw, rgb[1] * cw, rgb[2] * cw, cw], -1)
         om = f32(1) - s[..., 3]
         ns = s + col * om[..., None]
@@ -152,7 +162,7 @@ def _march(F, W, H, m, table, light, blend, density, brightness, toff, tscale, i
     out = np.where(out > 0, np.where(out > 1, f32(1), out), f32(0))
     out = np.where(hit[..., None], out, f32(0)).astype(np.float32)
     if info is not None:
-        info.update(samples=samples, flat=flat,
+        info.update(samples=samples, flat=flat, clamped=clamped,
                     c=np.concatenate(cs) if cs else np.zeros(0, np.float32))
     return pack(out), out, n.astype(np.int32)
 
