@@ -1037,7 +1037,22 @@ int vr_gmm_quantile_info(vr_extent *dims, const float **d_plane, uint64_t *plane
  *
  * At most one of this table and the 2-D table below is set: a successful
  * vr_set_transfer_function(non-NULL) clears the 2-D table; a NULL call clears only
- * this one. */
+ * this one.
+ *
+ * The order of the checks, where more than one refusal applies to a frame (it holds
+ * for both tables, the projection and the light below).  vr_render / render_kernel:
+ * first a gradient method whose plane is not resident (VR_ERR_UNSUPPORTED); then the
+ * volume the method reads (VR_ERR_STATE without it); then a record query's own state
+ * (methods 10-13: VR_ERR_STATE without it or with another bin count, as without a
+ * table); only then the light, the projection and the tables, in that order, each with
+ * its VR_ERR_UNSUPPORTED.  vr_render_gmm: the light, the projection and the tables
+ * first (VR_ERR_UNSUPPORTED), then the volume, the method and its state as without
+ * them.  vr_render_gmm_baked: a method without a GMM plane set (VR_ERR_UNSUPPORTED);
+ * then the light (with a projection or a 2-D table set, or with the plane set not
+ * baked: VR_ERR_UNSUPPORTED), a projection with a 2-D table, a 2-D table with the
+ * plane set not baked (both VR_ERR_UNSUPPORTED); then, as without any of them and so
+ * under a 1-D table or a projection too, VR_ERR_STATE for a plane set that is not baked
+ * or not complete; last the 2-D table's v plane set. */
 #define VR_TF_MAX 256
 int vr_set_transfer_function(const float *rgba, int n);
 int vr_transfer_function(float *rgba, int *n);
